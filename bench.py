@@ -8,24 +8,29 @@ Headline config: the reference's best 3D all-reduce data point — a bf16 activa
 
 One "step" = one in-place SUM all-reduce of that tensor on every rank. W untimed warmup steps,
 then EXACTLY K steps timed between [barrier + synchronize] and [synchronize]; the elapsed time is
-the MAX over ranks. busBW follows nccl-tests: ``bytes / t * 2(P-1)/P`` — identically 0 at P=1
-(no inter-GPU traffic), where ``vs_baseline`` is null (the reference has no P=1 data).
+the MAX over ranks. busBW follows nccl-tests: ``bytes / t * 2(P-1)/P``. At P=1 that factor is 0
+(no inter-GPU traffic): ``value`` is then ``bytes / t``, the throughput of the timed device copy
+(``value_is`` says which), and ``vs_baseline`` is null (the reference has no P=1 data).
 Per-GPU message size is fixed as N grows: weak scaling.
 
-Side measurements (also in the JSON line): p50 latency of a 512 B all-reduce (reference best
-22.9 µs at P=2, 32.0 µs at P=8) and busBW at 8 MiB (reference best 7.53 GB/s), the 1 KiB..1 GiB
-all-reduce sweep, and ``baseline_configs``: BASELINE configs 3 (3D activation-shaped
-all-gather + reduce-scatter grid), 4 (MoE uneven all-to-all) and 5 (GPT-2-small DDP step,
-B16 x T1024 per GPU) as isolated, validated, roofline-guarded, time-boxed sections
-(``bench/baseline_configs.py``) — a failing section records ``{"error": ...}`` and never costs
-the headline.
+A plain run does only that: set up, warm up, time the K steps, write the last step's result if
+``--dump-outputs DIR`` is given, print the JSON line. Everything below runs only with ``--full``.
+
+Side measurements (``--full``; also in the JSON line): p50 latency of a 512 B all-reduce
+(reference best 22.9 µs at P=2, 32.0 µs at P=8) and busBW at 8 MiB (reference best 7.53 GB/s),
+the 1 KiB..1 GiB all-reduce sweep, and ``baseline_configs``: BASELINE configs 3 (3D
+activation-shaped all-gather + reduce-scatter grid), 4 (MoE uneven all-to-all) and 5
+(GPT-2-small DDP step, B16 x T1024 per GPU) as isolated, validated, roofline-guarded,
+time-boxed sections (``bench/baseline_configs.py``) — a failing section records
+``{"error": ...}`` and never costs the headline.
 
 Whole-run deadline (``--deadline-s``, default 420 s, rank-agreed): the headline all-reduce is
 always measured and printed; every later part (remaining headline candidates, side runs, each
 sweep size, each BASELINE config section) first checks the deadline and, once it has passed, is
 recorded as ``skipped_deadline`` instead of run. ``wall_s`` in the JSON is the whole run.
 
-Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W]``; for N>1 launch with
+Usage: ``python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]``;
+for N>1 launch with
 ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py``.
 """
 
@@ -56,6 +61,20 @@ def parse(argv=None):
                     help="best = time RCCL through torch, RCCL through our native C++ engine and "
                          "the IPC xGMI kernel (if its self-test passed on every rank) during "
                          "warmup and run the fastest")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every side measurement: 512 B / 8 MiB side "
+                         "runs, the all-reduce size sweep, the same-message collectives, the "
+                         "virtual-rank emulation and the BASELINE config 3/4/5 sections (each can "
+                         "still be switched off with its --no-* option); a plain run measures "
+                         "the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (rank 0's "
+                         "all-reduce result) as float32 DIR/allreduce_out.npy; a fixed, seeded "
+                         "sample of the elements when the whole result would be too large. At "
+                         "more than one rank the timed all-reduce is in place and never reset, "
+                         "so that result is the input sum scaled by P per step run before it and "
+                         "leaves the bf16 range after some tens of steps: compare builds there "
+                         "with few steps")
     ap.add_argument("--no-side", action="store_true", help="skip the 512 B / 8 MiB side runs")
     ap.add_argument("--no-sweep", action="store_true", help="skip the all-reduce size sweep")
     ap.add_argument("--sweep-max-mib", type=int, default=1024,
@@ -265,9 +284,30 @@ def _timed_steps(comm, op, steps: int) -> float:
     return comm.allreduce_max(dt)
 
 
+DUMP_MAX_ELEMS = 1 << 23       # 32 MiB of float32 per dumped array
+
+
+def _dump_outputs(path: str, result) -> None:
+    """``path/allreduce_out.npy``: the all-reduce result of the last timed step as float32 — all
+    of it up to DUMP_MAX_ELEMS elements, else the elements at DUMP_MAX_ELEMS fixed positions
+    (seeded, sorted, the same for every run of the same shape)."""
+    import numpy as np
+    import torch
+
+    flat = result.reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        pos = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_MAX_ELEMS))
+        flat = flat[torch.from_numpy(pos).to(flat.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "allreduce_out.npy"),
+            flat.float().cpu().numpy().astype(np.float32, copy=False))
+
+
 def main(argv=None) -> int:
     t_start = time.perf_counter()
     args = parse(argv)
+    if not args.full:               # a plain run: set up, warm up, time the headline, report
+        args.no_side = args.no_configs = True
     import torch
 
     from distributed_llm_backend_benchmark_amd.bench.timing import time_per_iteration
@@ -373,9 +413,15 @@ def main(argv=None) -> int:
         op.ipc_kernel().raise_if_error()
     bus = busbw_gbps("allreduce", nbytes, per_step, P)
     alg = algbw_gbps("allreduce", nbytes, per_step, P)
+    # one rank: no inter-GPU link is in the path and the nccl-tests factor 2(P-1)/P is 0, which
+    # would make the headline a constant whatever the step took. The bus the message crosses
+    # is then device memory, once in each direction: the value is the step's own throughput
+    value = bus if P > 1 else alg
     why = too_fast("allreduce", nbytes, per_step, P)
     if why:
         raise SystemExit(f"{why}: {op_label} timed an empty call, refusing to report it")
+    if args.dump_outputs and comm.rank == 0:
+        _dump_outputs(args.dump_outputs, op.result())
 
     side = {}
     if not args.no_side and deadline.expired("side_512B_8MiB"):
@@ -517,7 +563,7 @@ def main(argv=None) -> int:
     if comm.rank == 0:
         rec = {
             "metric": "all-reduce bus BW (GB/s)",
-            "value": round(bus, 4),
+            "value": round(value, 4),
             "unit": "GB/s",
             "n_gpus": P,
             "steps": args.steps,
@@ -539,10 +585,13 @@ def main(argv=None) -> int:
                 "impl_trial_ms": {k: v * 1e3 for k, v in trial.items()} if len(trial) > 1 else None,
                 "impl_invalid": invalid or None,
             },
+            "value_is": "busbw" if P > 1 else "algbw",
+            "busbw_GBps": bus,
             "algbw_GBps": alg,
             "baseline_busbw_GBps": REF_BUSBW_GBPS,
-            "note": ("busBW = bytes/t*2(P-1)/P (nccl-tests); identically 0 at P=1, where "
-                     "vs_baseline is null (reference has no single-rank data)" +
+            "note": ("busBW = bytes/t*2(P-1)/P (nccl-tests); that factor is 0 at P=1, where "
+                     "value is bytes/t (algBW) and vs_baseline is null (reference has no "
+                     "single-rank data)" +
                      ("; P=1 step = out-of-place identity all-reduce (a device copy of the "
                       "message: real GPU work, algBW = copy throughput); in-place candidates "
                       "enqueue nothing at one rank and are excluded" if P == 1 else "")),

@@ -21,7 +21,7 @@ def _bench(extra_env=None):
     env = {k: v for k, v in os.environ.items() if k != "CUDA_VISIBLE_DEVICES"}
     env.update(extra_env or {})
     out = run_torchrun(2, [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3",
-                           "--warmup", "1"] + SMALL, 300, env=env)
+                           "--warmup", "1", "--full"] + SMALL, 300, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -55,6 +55,50 @@ def test_bench_sections_and_isolated_failure():
     for k in HEADLINE_KEYS:
         assert bad[k] == ok[k], k
     assert bad["value"] > 0 and bad["vs_baseline"] is not None
+
+
+FULL_ONLY_KEYS = ("allreduce_sweep", "baseline_configs", "collectives_same_message",
+                  "virtual_rank_emulation", "p50_latency_us_512B", "busbw_GBps_8MiB")
+
+
+def test_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without --full (gloo, world 1): the headline record only, no side measurement; with
+    --dump-outputs the last timed step's all-reduce result as float32, the same from run to
+    run, and equal to the seeded input (one rank: the sum is the message itself)."""
+    import numpy as np
+    import torch
+
+    from distributed_llm_backend_benchmark_amd.parallel.collectives import make_data
+
+    # the CPU path, also on a machine with a device
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+                              "--steps", "3", "--warmup", "1", "--shape", "2,64,256",
+                              "--dump-outputs", str(d)], capture_output=True, text=True,
+                             timeout=300, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        rec = json.loads(lines[0])
+        assert rec["metric"] == "all-reduce bus BW (GB/s)" and rec["unit"] == "GB/s"
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+        assert rec["higher_is_better"] is True and rec["dtype"] == "bf16"
+        # one rank: busBW is 0 by definition, the value is the timed step's bytes / t
+        assert rec["busbw_GBps"] == 0 and rec["value_is"] == "algbw"
+        want_gbps = 2 * 64 * 256 * 2 / (rec["ms_per_step"] * 1e-3) / 1e9
+        assert rec["value"] > 0 and abs(rec["value"] - want_gbps) <= 1e-3 * want_gbps + 1e-4
+        assert not [k for k in FULL_ONLY_KEYS if k in rec], sorted(rec)
+        assert os.listdir(d) == ["allreduce_out.npy"]
+        dumps.append(np.load(d / "allreduce_out.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2 * 64 * 256,)
+    assert np.array_equal(dumps[0], dumps[1])
+    # the message is generated on the device the run used (gloo: the CPU)
+    dev = torch.device("cpu" if rec["config"]["parallelism"].startswith("gloo") else "cuda:0")
+    want = make_data((2, 64, 256), torch.bfloat16, 0, dev).float().cpu().numpy()
+    assert np.array_equal(dumps[0], want.reshape(-1))
 
 
 def test_section_wrapper_world1_error_record():

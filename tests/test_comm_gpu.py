@@ -627,7 +627,8 @@ def test_ddp_comm_stream_is_normal_priority():
 
 def test_bench_py_world1():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5",
-                          "--warmup", "2"], capture_output=True, text=True, timeout=600, cwd=REPO)
+                          "--warmup", "2", "--full"], capture_output=True, text=True,
+                         timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     rec = json.loads(line)
@@ -663,6 +664,40 @@ def test_bench_py_world1():
     assert r["loss"] < r["loss_first_step"] + 1.0 and r["bucket_paths"] == {"none": r["buckets"]}
 
 
+def test_bench_py_world1_plain_run_dumps_outputs(tmp_path):
+    """Without --full: the headline (the out-of-place copy through the native engine) and
+    nothing else; --dump-outputs writes a float32 sample of the last step's result, within the
+    64 MB bound, every value one of the seeded bf16 message."""
+    import numpy as np
+
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps",
+                          "5", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    assert rec["n_gpus"] == 1 and rec["steps"] == 5 and rec["ms_per_step"] > 0
+    assert rec["config"]["impl"] == "native_oop" and 0 < rec["algbw_GBps"] <= 8000.0
+    # one rank: busBW is 0 by definition, the value is the timed copy's bytes / t
+    assert rec["busbw_GBps"] == 0 and rec["value_is"] == "algbw"
+    want_gbps = (64 << 20) / (rec["ms_per_step"] * 1e-3) / 1e9
+    assert abs(rec["value"] - want_gbps) <= 1e-3 * want_gbps
+    for k in ("allreduce_sweep", "baseline_configs", "virtual_rank_emulation",
+              "p50_latency_us_512B"):
+        assert k not in rec, k
+    assert os.listdir(tmp_path) == ["allreduce_out.npy"]
+    got = np.load(tmp_path / "allreduce_out.npy")
+    # 32 Mi elements do not fit the bound: the sample is 8 Mi of them, 32 MiB
+    assert got.dtype == np.float32 and got.size == 1 << 23 and got.nbytes <= 64 << 20
+    from distributed_llm_backend_benchmark_amd.parallel.collectives import make_data
+
+    data = make_data((8, 2048, 2048), torch.bfloat16, 0, torch.device("cuda", 0))
+    pos = np.sort(np.random.default_rng(0).integers(0, data.numel(), size=got.size))
+    want = data.reshape(-1)[torch.from_numpy(pos).cuda()].float().cpu().numpy()
+    assert np.array_equal(got, want)
+
+
 def test_bench_py_two_ranks_rehearsal():
     """bench.py's multi-rank path (candidate agreement, IPC kernel, native-engine refusal of a
     shared GPU) with 2 ranks on one GPU over a gloo process group (DLBB_BENCH_BACKEND=gloo)."""
@@ -670,7 +705,7 @@ def test_bench_py_two_ranks_rehearsal():
 
     env = dict(os.environ, DLBB_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = run_torchrun(2, [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "5",
-                           "--warmup", "2", "--sweep-max-mib", "32", "--grid",
+                           "--warmup", "2", "--full", "--sweep-max-mib", "32", "--grid",
                            "2,1024,1024;1,2048,2048", "--moe", "2048,1024", "--ddp-model",
                            "2,4,256,4096,4,256", "--ddp-steps", "4"], 600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -402,7 +402,7 @@ def test_bench_py_gloo_world2_contract():
 
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--shape", "1,64,256", "--sweep-max-mib", "1"]
+           "--full", "--shape", "1,64,256", "--sweep-max-mib", "1"]
     env = {k: v for k, v in os.environ.items() if k not in ("CUDA_VISIBLE_DEVICES",)}
     out = run_torchrun(2, cmd, 300, env=env, cwd=repo)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -428,7 +428,7 @@ def test_bench_py_deadline_keeps_the_headline():
 
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--shape", "1,64,256", "--sweep-max-mib", "1", "--deadline-s", "0"]
+           "--full", "--shape", "1,64,256", "--sweep-max-mib", "1", "--deadline-s", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("CUDA_VISIBLE_DEVICES",)}
     out = run_torchrun(2, cmd, 300, env=env, cwd=repo)
     assert out.returncode == 0, out.stderr[-3000:]

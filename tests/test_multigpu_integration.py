@@ -40,7 +40,7 @@ def test_bench_py_across_gpus():
     candidate validated, busBW physically plausible (per-GPU xGMI: 7 links)."""
     n = _ngpus()
     out = _torchrun(n, [os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "10",
-                        "--warmup", "3", "--sweep-max-mib", "64"])
+                        "--warmup", "3", "--full", "--sweep-max-mib", "64"])
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == n and rec["steps"] == 10 and rec["warmup"] == 3
     assert 0 < rec["value"] < 2000.0, rec["value"]

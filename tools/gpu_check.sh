@@ -23,7 +23,7 @@ for step in "$@"; do
   case $step in
     tests) run pytest_gpu 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     *) run "custom" 900 bash -c "$step" ;;
   esac
 done

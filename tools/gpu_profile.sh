@@ -18,7 +18,7 @@ for what in "$@"; do case $what in
   gpt2) step prof_gpt2 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof_gpt2" -o gpt2 -- \
         python3 -m distributed_llm_backend_benchmark_amd.cli.train_ddp --steps 5 --warmup 2 ;;
   bench) step prof_bench 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof_bench" -o bench -- \
-        python3 "$R/bench.py" --steps 20 --warmup 5 ;;
+        python3 "$R/bench.py" --steps 20 --warmup 5 --full ;;
   kbench) step kbench 900 python3 "$R/tools/bench_kernels.py" gemm mem ;;
   tpbench) step tp7b 900 python3 -m distributed_llm_backend_benchmark_amd.cli.run_tp --config "$R/config/7b_config.yaml" --backend rccl --output-dir "$R/gpurun_out/tp" &&
            step tp7b_torch 900 python3 -m distributed_llm_backend_benchmark_amd.cli.run_tp --config "$R/config/7b_config.yaml" --backend rccl --kernels torch --output-dir "$R/gpurun_out/tp_torch" ;;

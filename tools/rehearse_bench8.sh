@@ -9,7 +9,7 @@ OUT=$1
 HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 DLBB_BENCH_BACKEND=gloo timeout -k 10 700 python -m torch.distributed.run --standalone \
-  --local-addr 127.0.0.1 --nproc-per-node 8 bench.py --gpus 8 --steps 5 --warmup 2 \
+  --local-addr 127.0.0.1 --nproc-per-node 8 bench.py --gpus 8 --steps 5 --warmup 2 --full \
   --deadline-s 420 > "$OUT.log" 2>&1
 rc=$?
 grep '^{' "$OUT.log" | tail -1 > "$OUT"
