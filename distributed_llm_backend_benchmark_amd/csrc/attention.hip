@@ -852,6 +852,381 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_bwd_dq_d64_kernel(AttnBw
   wg_stamp(a.stamps, 2);
 }
 
+// ----------------------------------------------------------------------- backward, head dim 128
+// The same two kernels for 128-wide heads. Every [rows][128 x bf16] operand is staged as TWO
+// bswz images of 64 rows x 128 B, dims 0-63 then dims 64-127 (kSliceImg apart), so stage64,
+// row_operand, tr_lane_off and tr_operand_at apply unchanged (the second image is the reads'
+// IMG immediate) and both read patterns stay conflict-free. k-step ks of S / dP reads image
+// ks >> 2, chunk 2 (ks & 3) + hi; 32-dim block dt of dQ^T / dK^T / dV^T reads image dt >> 1 with
+// parity dt & 1. No atomics: run-to-run bit-identical like the D = 64 pair.
+// Measured (profiles/attn_d128_bwd/, both kernels): 188.8 us at 16 x 1024 x 6 x 128 against
+// 540.9 us for the library flash backward + pack_rows it replaces (the D = 64 pair: 136.0 us at
+// equal FLOPs); 577.0 against 1721.3 us at 4 x 4096 x 8 x 128.
+constexpr int kD128 = 128;
+constexpr int kImg128 = 2 * kSliceImg;       // 64 rows x 256 B as two images (16 KiB)
+
+// tr_operand_at with the 16-row step as a value (a constant once the caller's loops unroll)
+template <int IMG>
+__device__ __forceinline__ bf16x8 tr_operand_sel(int sel, const char* same, const char* flip) {
+  switch (sel) {
+    case 0: return tr_operand_at<0, IMG>(same, flip);
+    case 1: return tr_operand_at<16, IMG>(same, flip);
+    case 2: return tr_operand_at<32, IMG>(same, flip);
+    default: return tr_operand_at<48, IMG>(same, flip);
+  }
+}
+// 32-dim block dt (0..3) of a two-image operand, rows 16 sel .. 16 sel + 15; p0 / p1 = first
+// image + tr_lane_off(lane, 0 / 1)
+__device__ __forceinline__ bf16x8 tr_operand_d128(int sel, int dt, const char* p0,
+                                                  const char* p1) {
+  const char* same = (dt & 1) ? p1 : p0;
+  const char* flip = (dt & 1) ? p0 : p1;
+  return dt < 2 ? tr_operand_sel<0>(sel, same, flip) : tr_operand_sel<kSliceImg>(sel, same, flip);
+}
+
+// dK/dV, head dim 128: as the D = 64 kernel, a workgroup owns 128 keys and a wave 32 (key on the
+// MFMA lane) with their K / V fragments (64 registers) and dK^T / dV^T accumulators (128) in
+// registers. With S, dP, operands and addresses that is past 256, so one wave per SIMD
+// (__launch_bounds__(256, 1), the CDNA guide's form for D = 128): 336 registers, no spill.
+// Q / dO slices of 64 queries, double buffered (2 x 32 KiB + the row constants). Otherwise the
+// D = 64 kernel's structure: row constants as the accumulators' start, mask behind a wave-uniform
+// branch, causal pairing, asm transposed reads with immediates.
+// Only this form was run: 131 us of the 188.8 at 16 x 1024 x 6 x 128, whose 384 workgroups at one
+// per CU make two rounds on 256 CUs (profiles/attn_d128_bwd/attn_timeline_*.jsonl). Compiled and
+// not kept: this kernel for two waves per SIMD (18 spilled VGPRs); 64 keys per wave at one wave
+// per SIMD, the Q / dO reads shared by two 32-key halves (448 registers for fragments and
+// accumulators alone: 64 spilled VGPRs). Not built: two waves per SIMD with the K / V block
+// resident in LDS (64 KiB per workgroup, which leaves 16 KiB each for Q / dO slices if two
+// workgroups share a CU's 160 KiB).
+__global__ void __launch_bounds__(kAttnThreads, 1) attn_bwd_dkdv_d128_kernel(AttnBwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 31, hi = lane >> 5;
+  int blk, h, b;
+  head_block(a.xcd, blk, h, b);
+  // causal pairing: key blocks blk (more query slices) and nkb-1-blk, equal work per workgroup
+  const int nkb = (a.T + kBwdKeys - 1) / kBwdKeys;
+  const int npass = nkb - 1 - blk != blk ? 2 : 1;
+  wg_stamp(a.stamps, 0);
+  for (int pass = 0; pass < npass; ++pass) {
+    if (pass) wg_stamp(a.stamps, 1);
+    if (pass) __syncthreads();                    // every wave done with the LDS ring
+    const int kb0 = (pass == 0 ? blk : nkb - 1 - blk) * kBwdKeys;   // heaviest (block 0) first
+    const int kw = kb0 + wave * 32;
+    const uint16_t* base_bt = a.qkv + static_cast<int64_t>(b) * a.T * a.ld;
+    const uint16_t* dout_bt = a.dout + static_cast<int64_t>(b) * a.T * a.ldo;
+    const int hoff = h * kD128;
+    const int64_t bh = static_cast<int64_t>(b) * a.H + h;
+    const float* lrow = a.nls + bh * a.T;            // -LSE * sqrt(D)
+    const float* drow = a.delta + bh * a.T;          // -delta
+
+    bf16x8 kf[8], vf[8];
+    const int mykey = kw + r;
+    {
+      const int kk = mykey < a.T ? mykey : a.T - 1;
+      const uint16_t* kp = base_bt + static_cast<int64_t>(kk) * a.ld + kD128 * a.H + hoff + 8 * hi;
+      const uint16_t* vp = kp + kD128 * a.H;
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        kf[ks] = *reinterpret_cast<const bf16x8*>(kp + 16 * ks);
+        vf[ks] = *reinterpret_cast<const bf16x8*>(vp + 16 * ks);
+      }
+    }
+    f32x16 dv[4], dk[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) { dv[dt][e] = 0.f; dk[dt][e] = 0.f; }
+
+    const int ns = (a.T - kb0 + kSlice - 1) / kSlice;
+    auto imgQ = [&](int c) { return smem + c * 2 * kImg128; };
+    auto imgG = [&](int c) { return smem + c * 2 * kImg128 + kImg128; };
+    // per-slice row constants by LDS-DMA beside the images (as the D = 64 kernel)
+    auto rowv = [&](int c) { return reinterpret_cast<float*>(smem + 4 * kImg128 + c * 512); };
+    auto stage_all = [&](int q0, int c) {
+      stage64(base_bt + hoff, a.ld, q0, a.T, imgQ(c), wave, lane);
+      stage64(base_bt + hoff + 64, a.ld, q0, a.T, imgQ(c) + kSliceImg, wave, lane);
+      stage64(dout_bt + hoff, a.ldo, q0, a.T, imgG(c), wave, lane);
+      stage64(dout_bt + hoff + 64, a.ldo, q0, a.T, imgG(c) + kSliceImg, wave, lane);
+      if (wave < 2) {
+        int t = q0 + lane;
+        t = t < a.T ? t : a.T - 1;
+        __builtin_amdgcn_global_load_lds((wave == 0 ? lrow : drow) + t,
+                                         (lds_vptr_t)(rowv(c) + 64 * wave), 4, 0, 0);
+      }
+    };
+    stage_all(kb0, 0);
+    for (int i = 0; i < ns; ++i) {
+      const int cur = i & 1;
+      const int qs = kb0 + i * kSlice;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();                   // publishes slice i, frees buffer cur^1
+      if (i + 1 < ns) stage_all(qs + kSlice, cur ^ 1);
+      const char* iq = imgQ(cur);
+      const char* ig = imgG(cur);
+      const float* rv = rowv(cur);
+      // transposed-read lane addresses of this slice's images (parity 0 / 1, tr_operand_at)
+      const char* gq0 = iq + tr_lane_off(lane, 0);
+      const char* gq1 = iq + tr_lane_off(lane, 1);
+      const char* gg0 = ig + tr_lane_off(lane, 0);
+      const char* gg1 = ig + tr_lane_off(lane, 1);
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub) {
+        const int qsub = qs + 32 * sub;
+        if (qsub + 31 < kw) continue;                 // wave-uniform: every query < every key
+        const int rb = 32 * sub;                      // image row base of this 32-query block
+        // row constants of rows q = qsub + 8 g + 4 hi + u (register e = 4 g + u) as the
+        // accumulators' starting values: S' = Q K^T - LSE sqrt(D), dP' = dO V^T - delta (asm
+        // reads of a DMA-filled region)
+        f32x4 lv[4], dv4[4];
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          lv[g4] = ds_read_b128_asm(rv + rb + 8 * g4 + 4 * hi);
+          dv4[g4] = ds_read_b128_asm(rv + 64 + rb + 8 * g4 + 4 * hi);
+        }
+        tr_wait(lv[0], lv[1], lv[2], lv[3], dv4[0], dv4[1], dv4[2], dv4[3]);
+        f32x16 s, dp;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          s[e] = lv[e >> 2][e & 3];
+          dp[e] = dv4[e >> 2][e & 3];
+        }
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+          const int im = (ks >> 2) * kSliceImg, ch = 2 * (ks & 3) + hi;
+          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(iq + im, rb + r, ch), kf[ks], s,
+                                                      0, 0, 0);
+          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(ig + im, rb + r, ch), vf[ks],
+                                                       dp, 0, 0, 0);
+        }
+        // mask the raw scores (exp2(-inf) = 0) only on the diagonal or past T: wave-uniform
+        const bool diag = qsub < kw + 31;
+        if (diag || qsub + 31 >= a.T) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int q = qsub + (e & 3) + 8 * (e >> 2) + 4 * hi;
+            if ((diag && mykey > q) || q >= a.T) s[e] = -INFINITY;
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const float p = __builtin_amdgcn_exp2f(s[e] * a.scale_log2);
+          s[e] = p;
+          dp[e] = p * dp[e];
+        }
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+          const bf16x8 pb = acc_to_bf16(s, st);
+          const bf16x8 db = acc_to_bf16(dp, st);
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) {
+            // dO^T, Q^T (asm reads; row offset and image in the immediate)
+            bf16x8 gt = tr_operand_d128(2 * sub + st, dt, gg0, gg1);
+            bf16x8 qt = tr_operand_d128(2 * sub + st, dt, gq0, gq1);
+            tr_wait(gt, qt);
+            dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gt, pb, dv[dt], 0, 0, 0);
+            dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt, db, dk[dt], 0, 0, 0);
+          }
+        }
+      }
+    }
+    if (mykey < a.T) {
+      uint16_t* dkp = a.dqkv + (static_cast<int64_t>(b) * a.T + mykey) * a.ld + kD128 * a.H + hoff;
+      uint16_t* dvp = dkp + kD128 * a.H;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          u16x4 wk, wv;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            wk[u] = f32_to_bf16(dk[dt][4 * gg + u] * a.scale);
+            wv[u] = f32_to_bf16(dv[dt][4 * gg + u]);
+          }
+          *reinterpret_cast<u16x4*>(dkp + dt * 32 + 8 * gg + 4 * hi) = wk;
+          *reinterpret_cast<u16x4*>(dvp + dt * 32 + 8 * gg + 4 * hi) = wv;
+        }
+    }
+  }
+  wg_stamp(a.stamps, 2);
+}
+
+// dQ, head dim 128: 128 queries per workgroup (wave: 32, query on the lane) over 64-key K / V
+// tiles, each two images (K dims 0-63, K dims 64-127, V likewise: 32 KiB per tile, double
+// buffered). Q / dO fragments 64 registers, dQ^T 64, S^T / dP^T 32: two waves per SIMD.
+// Computes -delta and -LSE sqrt(D) of its queries for the dK/dV kernel.
+__global__ void __launch_bounds__(kAttnThreads, 2) attn_bwd_dq_d128_kernel(AttnBwdArgs a) {
+  constexpr int TILE = 2 * kImg128;                // K + V
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nqb = (a.T + kQB - 1) / kQB;
+  int blk, h, b;
+  head_block(a.xcd, blk, h, b);
+  // causal pairing as the forward: query blocks nqb-1-blk then blk, equal work per workgroup
+  const int npass = nqb - 1 - blk != blk ? 2 : 1;
+  wg_stamp(a.stamps, 0);
+  for (int pass = 0; pass < npass; ++pass) {
+    if (pass) wg_stamp(a.stamps, 1);
+    if (pass) __syncthreads();                    // every wave done with the LDS ring
+    const int qb = pass == 0 ? nqb - 1 - blk : blk;
+    const int q0 = qb * kQB;
+    const int qw = q0 + wave * 32;
+    const int r = lane & 31, hi = lane >> 5;
+    const uint16_t* base_bt = a.qkv + static_cast<int64_t>(b) * a.T * a.ld;
+    const int hoff = h * kD128;
+    const int64_t bh = static_cast<int64_t>(b) * a.H + h;
+    const int qme = qw + r;
+    const int qc = qme < a.T ? qme : a.T - 1;
+
+    bf16x8 qf[8], gf[8];
+    {
+      const uint16_t* qp = base_bt + static_cast<int64_t>(qc) * a.ld + hoff + 8 * hi;
+      const uint16_t* gp = a.dout + (static_cast<int64_t>(b) * a.T + qc) * a.ldo + hoff + 8 * hi;
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
+        gf[ks] = *reinterpret_cast<const bf16x8*>(gp + 16 * ks);
+      }
+    }
+    // the row constants of this lane's query (always the fuse_delta form here: no delta pass),
+    // written for the dK/dV kernel: delta = dO . O over the 128 dims (8 per (ks, hi) fragment,
+    // halves joined by lane ^ 32)
+    float nl2, nd;                                   // -LSE * log2(e), -delta
+    {
+      const uint16_t* op = a.out + (static_cast<int64_t>(b) * a.T + qc) * a.ldo + hoff + 8 * hi;
+      float acc = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        const bf16x8 of = *reinterpret_cast<const bf16x8*>(op + 16 * ks);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          acc += bf16_to_f32(static_cast<uint16_t>(gf[ks][j])) *
+                 bf16_to_f32(static_cast<uint16_t>(of[j]));
+      }
+      const float other = __shfl_xor(acc, 32, 64);
+      nd = -(hi == 0 ? acc + other : other + acc);   // (even chunks) + (odd chunks) in both halves
+      const float nls = -a.lse[bh * a.T + qc] / a.scale;   // -LSE * sqrt(D)
+      nl2 = nls * a.scale_log2;
+      if (hi == 0 && qme < a.T) {
+        a.delta[bh * a.T + qme] = nd;
+        a.nls[bh * a.T + qme] = nls;
+      }
+    }
+    f32x16 dq[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) dq[dt][e] = 0.f;
+    const int q_hi = qw + 31;
+    const int last_key = (q0 + kQB - 1) < (a.T - 1) ? (q0 + kQB - 1) : (a.T - 1);
+    const int nt = last_key / kKB + 1;
+    auto tileK = [&](int c) { return smem + c * TILE; };
+    auto tileV = [&](int c) { return smem + c * TILE + kImg128; };
+    // this lane's K sources for image rows wave * 16 + i * 8 + lane / 8 of tile 0, dims 0-63
+    // (dims 64-127: + 64; V: + D H); a tile adds one uniform offset, rows clamped only on the
+    // tile that crosses T
+    const uint16_t* ksrc[2];
+    {
+      const int r_in = lane >> 3, slot = lane & 7;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int row = wave * 16 + i * 8 + r_in;
+        ksrc[i] = base_bt + static_cast<int64_t>(row) * a.ld + hoff + (slot ^ bswz(row)) * 8 +
+                  kD128 * a.H;
+      }
+    }
+    auto stage = [&](int k0, char* tk, char* tv) {
+      if (k0 + kKB <= a.T) {                          // wave-uniform: no row past T
+        const int64_t off = static_cast<int64_t>(k0) * a.ld;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int ro = (wave * 16 + i * 8) * 128;
+          attn_glds16(ksrc[i] + off, tk + ro);
+          attn_glds16(ksrc[i] + off + 64, tk + kSliceImg + ro);
+          attn_glds16(ksrc[i] + off + kD128 * a.H, tv + ro);
+          attn_glds16(ksrc[i] + off + kD128 * a.H + 64, tv + kSliceImg + ro);
+        }
+        return;
+      }
+      const uint16_t* kb = base_bt + hoff + kD128 * a.H;
+      stage64(kb, a.ld, k0, a.T, tk, wave, lane);
+      stage64(kb + 64, a.ld, k0, a.T, tk + kSliceImg, wave, lane);
+      stage64(kb + kD128 * a.H, a.ld, k0, a.T, tv, wave, lane);
+      stage64(kb + kD128 * a.H + 64, a.ld, k0, a.T, tv + kSliceImg, wave, lane);
+    };
+    stage(0, tileK(0), tileV(0));
+    for (int kt = 0; kt < nt; ++kt) {
+      const int cur = kt & 1;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();                   // publishes tile kt, frees buffer cur^1
+      if (kt + 1 < nt) stage((kt + 1) * kKB, tileK(cur ^ 1), tileV(cur ^ 1));
+      const int k0 = kt * kKB;
+      if (k0 <= q_hi) {
+        const char* tk = tileK(cur);
+        const char* tv = tileV(cur);
+        // K^T transposed-read lane addresses (parity 0 / 1); row offset, image: the immediate
+        const char* tk0 = tk + tr_lane_off(lane, 0);
+        const char* tk1 = tk + tr_lane_off(lane, 1);
+        const bool diag = k0 + kKB - 1 > qw;           // wave-uniform: a key beyond a query
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          f32x16 s, dp;
+#pragma unroll
+          for (int e = 0; e < 16; ++e) { s[e] = 0.f; dp[e] = 0.f; }
+#pragma unroll
+          for (int ks = 0; ks < 8; ++ks) {
+            const int im = (ks >> 2) * kSliceImg, ch = 2 * (ks & 3) + hi;
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(tk + im, kk * 32 + r, ch),
+                                                        qf[ks], s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_operand(tv + im, kk * 32 + r, ch),
+                                                         gf[ks], dp, 0, 0, 0);
+          }
+          // causal mask on the raw scores of diagonal tiles only (exp2 of -inf is the zero
+          // probability); keys past T are > every query, so the same compare covers them
+          if (diag) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const int key = k0 + kk * 32 + (e & 3) + 8 * (e >> 2) + 4 * hi;
+              if (key > qme) s[e] = -INFINITY;
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], a.scale_log2, nl2));
+            dp[e] = p * (dp[e] + nd);
+          }
+#pragma unroll
+          for (int st = 0; st < 2; ++st) {
+            bf16x8 kt4[4];                            // K^T operands (asm reads)
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) kt4[dt] = tr_operand_d128(kk * 2 + st, dt, tk0, tk1);
+            const bf16x8 db = acc_to_bf16(dp, st);
+            tr_wait(kt4[0], kt4[1], kt4[2], kt4[3]);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+              dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt4[dt], db, dq[dt], 0, 0, 0);
+          }
+        }
+      }
+    }
+    if (qme < a.T) {
+      uint16_t* dqp = a.dqkv + (static_cast<int64_t>(b) * a.T + qme) * a.ld + hoff;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          u16x4 w;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) w[u] = f32_to_bf16(dq[dt][4 * gg + u] * a.scale);
+          *reinterpret_cast<u16x4*>(dqp + dt * 32 + 8 * gg + 4 * hi) = w;
+        }
+    }
+  }
+  wg_stamp(a.stamps, 2);
+}
+
 }  // namespace dlbb
 
 using namespace dlbb;
@@ -890,9 +1265,9 @@ DLBB_API int dlbb_attn_fwd(const void* qkv, int64_t ld, void* out, int64_t ldo, 
   return hipGetLastError();
 }
 
-// Backward of dlbb_attn_fwd (D = 64). dout / out: [B, T, H, 64] (row stride ldo); lse:
+// Backward of dlbb_attn_fwd (D = 64 or 128). dout / out: [B, T, H, D] (row stride ldo); lse:
 // forward's; delta: [2, B, H, T] fp32 workspace (-delta, -LSE sqrt(D), produced by the dQ
-// kernel for the dK/dV kernel after it); dqkv: [B, T, 3, H, 64] (row stride ld, written fully).
+// kernel for the dK/dV kernel after it); dqkv: [B, T, 3, H, D] (row stride ld, written fully).
 // (Round-5 A/B forms removed in round 6: the dK/dV kernel concurrently on a side stream — its
 // backward 5 % faster alone, the GPT-2 step 0.25 ms slower; a separate delta pass; per-row DMA
 // addresses in dQ / incremental ones in dK/dV — each measured slower.)
@@ -900,7 +1275,7 @@ DLBB_API int dlbb_attn_bwd(const void* qkv, int64_t ld, const void* out, const v
                            int64_t ldo, const float* lse, float* delta, void* dqkv, int B, int T,
                            int H, int D, float scale, hipStream_t stream) {
   if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
-  if (D != kAttnD) return hipErrorInvalidValue;
+  if (D != kAttnD && D != kD128) return hipErrorInvalidValue;
   if (ld % 8 || ldo % 8 || ld < 3 * H * D || ldo < H * D) return hipErrorInvalidValue;
   auto mis16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (mis16(qkv) || mis16(out) || mis16(dout) || mis16(dqkv)) return hipErrorInvalidValue;
@@ -913,6 +1288,13 @@ DLBB_API int dlbb_attn_bwd(const void* qkv, int64_t ld, const void* out, const v
   // both kernels pair a heavy and a light causal block per workgroup (see the forward)
   const dim3 gq(((T + kQB - 1) / kQB + 1) / 2, H, B),
       gk(((T + kBwdKeys - 1) / kBwdKeys + 1) / 2, H, B);
+  if (D == kD128) {
+    hipLaunchKernelGGL(attn_bwd_dq_d128_kernel, gq, dim3(kAttnThreads), 4 * kImg128, stream, a);
+    a.stamps = g_stamps_dkdv;
+    hipLaunchKernelGGL(attn_bwd_dkdv_d128_kernel, gk, dim3(kAttnThreads), 4 * kImg128 + 1024,
+                       stream, a);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(attn_bwd_dq_d64_kernel<true>, gq, dim3(kAttnThreads), 4 * kTileKV, stream,
                      a);
   a.stamps = g_stamps_dkdv;

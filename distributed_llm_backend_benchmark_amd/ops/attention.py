@@ -4,11 +4,11 @@
 tensor-parallel rank's shard, models/tp_transformer.py) and returns ``[B, T, C]`` (heads
 interleaved, ready for the projection GEMM). The forward is our gfx950 flash kernel (head dim 64
 or 128); it reads Q/K/V straight out of ``qkv`` — no unbind/transpose copies — and emits the
-per-row log-sum-exp. The backward (head dim 64) is ours too (a query-block kernel for dQ that
-also writes the row constants, then a key-block kernel for dK/dV, no atomics), writing the fused
-``[B, T, 3C]`` gradient directly. At head dim 128 the backward is the stack's flash backward on
-our forward's O / LSE (``attn_bwd_library``: same natural-log ``[B, H, T]`` convention; no
-training path here uses it — the TP model is forward only).
+per-row log-sum-exp. The backward (head dim 64 or 128) is ours too (a query-block kernel for dQ
+that also writes the row constants, then a key-block kernel for dK/dV, no atomics: bit-identical
+from run to run), writing the fused ``[B, T, 3C]`` gradient directly. ``attn_bwd_library`` (the
+stack's flash backward on our forward's O / LSE, same natural-log ``[B, H, T]`` convention) is
+kept as the A/B baseline only; no autograd path calls it.
 
 Other head dims, CPU tensors and ``DLBB_KERNELS=torch`` use ``F.scaled_dot_product_attention``.
 """
@@ -72,14 +72,13 @@ class _CausalAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         qkv, out, lse = ctx.saved_tensors
-        if (qkv.shape[2] // 3) // ctx.n_head != 64:
-            return attn_bwd_library(qkv, out, lse, gout.contiguous(), ctx.n_head), None
         return attn_bwd(qkv, out, lse, gout, ctx.n_head), None
 
 
 def attn_bwd(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, gout: torch.Tensor,
              n_head: int) -> torch.Tensor:
-    """Raw backward: dQKV [B, T, 3C] (dkdv + dq kernels, no atomics)."""
+    """Raw backward, head dim 64 or 128: dQKV [B, T, 3C] (dq + dkdv kernels, no atomics).
+    ``gout`` may be any view; it is made contiguous."""
     B, T, C3 = qkv.shape
     C = C3 // 3
     D = C // n_head
@@ -95,7 +94,7 @@ def attn_bwd(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, gout: torc
 
 def attn_bwd_library(qkv, out, lse, gout, n_head: int) -> torch.Tensor:
     """The stack's flash backward on our forward's (O, LSE), dQ/dK/dV packed into [B, T, 3C]
-    (head dim 128, and the A/B baseline for :func:`attn_bwd`)."""
+    (the A/B baseline for :func:`attn_bwd`, tools/attn_bench.py; not on any autograd path)."""
     B, T, C3 = qkv.shape
     C = C3 // 3
     D = C // n_head

@@ -44,7 +44,6 @@ for B, T, H, D in ((16, 1024, 12, 64), (8, 2048, 12, 64), (4, 4096, 16, 64),
            "fwd_bwd_us_ours": t_fb_ours * 1e6, "fwd_bwd_us_torch": t_fb_torch * 1e6}
     t_lib = t_best(lambda: attn_bwd_library(qkv, o, lse, go, H), iters=10, rounds=3)
     rec["bwd_us_library"] = t_lib * 1e6
-    if D == 64:
-        t_bwd = t_best(lambda: attn_bwd(qkv, o, lse, go, H), iters=10, rounds=3)
-        rec.update(bwd_us_ours=t_bwd * 1e6, bwd_tflops_ours=2.5 * fl / t_bwd / 1e12)
+    t_bwd = t_best(lambda: attn_bwd(qkv, o, lse, go, H), iters=10, rounds=3)
+    rec.update(bwd_us_ours=t_bwd * 1e6, bwd_tflops_ours=2.5 * fl / t_bwd / 1e12)
     print(json.dumps(rec), flush=True)

@@ -4,8 +4,8 @@ CU it ran on. Reports kernel span, workgroup duration spread, start-time spread 
 later rounds) and how many workgroups each CU held at once — the residency that the PMC
 estimate (SQ_WAVE_CYCLES x 4 / kernel cycles) only gives as an average.
 
-    python tools/attn_timeline.py [B T H] [--dump=DIR]   (default: the GPT-2 shape 16 1024 12,
-    D = 64; --dump saves the last repetition's raw stamps as .npy)
+    python tools/attn_timeline.py [B T H [D]] [--dump=DIR]   (default: the GPT-2 shape
+    16 1024 12, D = 64 or 128; --dump saves the last repetition's raw stamps as .npy)
 """
 import json
 import os
@@ -65,7 +65,7 @@ def main():
     xcd = next((int(x.split("=", 1)[1]) for x in sys.argv[1:] if x.startswith("--xcd=")), None)
     dump = next((x.split("=", 1)[1] for x in sys.argv[1:] if x.startswith("--dump=")), None)
     B, T, H = (int(x) for x in args[:3]) if len(args) >= 3 else (16, 1024, 12)
-    D = 64
+    D = int(args[3]) if len(args) >= 4 else 64
     g = torch.Generator(device="cuda").manual_seed(0)
     qkv = torch.randn(B, T, 3 * H * D, device="cuda", generator=g).to(torch.bfloat16)
     gout = torch.randn(B, T, H * D, device="cuda", generator=g).to(torch.bfloat16)
