@@ -15,6 +15,8 @@ LayerNorm, so the block is ``LN1 → QKV → out-proj → AR → (add+LN2) → u
 (add+LN1 of the next block)``. ``attention="sdpa"`` swaps the stub for real causal attention
 (torch SDPA), ``attention="flash"`` for our causal flash kernel (``ops.causal_attention``).
 ``overlap_chunks`` > 1 interleaves micro-batches so the all-reduces run under GEMMs (forward()).
+``gemm_dtype="fp8"`` runs the four linears of every block through the FP8 GEMM (``ops.fp8``:
+per-token activation scales, per-output-row weight scales); the default stays bf16.
 """
 
 from __future__ import annotations
@@ -67,7 +69,7 @@ class TransformerBlock(nn.Module):
     def __init__(self, hidden_size: int, num_heads: int, ffn_intermediate: int, comm: Comm,
                  generator=None, init_std: float = 1.0, allreduce: str = "rccl",
                  allreduce_dtype: str = "bf16", attention: str = "slice",
-                 kernels: str = "hip"):
+                 kernels: str = "hip", gemm_dtype: str = "bf16"):
         super().__init__()
         P = comm.world_size
         self.hidden_size, self.num_heads, self.P = hidden_size, num_heads, P
@@ -76,16 +78,20 @@ class TransformerBlock(nn.Module):
         dev = comm.device
         self.ln1 = LayerNormParams(hidden_size, dev)
         self.qkv_proj = ColumnParallelLinear(hidden_size, 3 * hidden_size, comm,
-                                             generator=generator, std=init_std, kernels=kernels)
+                                             generator=generator, std=init_std, kernels=kernels,
+                                             gemm_dtype=gemm_dtype)
         self.out_proj = RowParallelLinear(hidden_size, hidden_size, comm, generator=generator,
                                           std=init_std, allreduce=allreduce,
-                                          allreduce_dtype=allreduce_dtype, kernels=kernels)
+                                          allreduce_dtype=allreduce_dtype, kernels=kernels,
+                                          gemm_dtype=gemm_dtype)
         self.ln2 = LayerNormParams(hidden_size, dev)
         self.ffn_up = ColumnParallelLinear(hidden_size, ffn_intermediate, comm,
-                                           generator=generator, std=init_std, kernels=kernels)
+                                           generator=generator, std=init_std, kernels=kernels,
+                                           gemm_dtype=gemm_dtype)
         self.ffn_down = RowParallelLinear(ffn_intermediate, hidden_size, comm,
                                           generator=generator, std=init_std, allreduce=allreduce,
-                                          allreduce_dtype=allreduce_dtype, kernels=kernels)
+                                          allreduce_dtype=allreduce_dtype, kernels=kernels,
+                                          gemm_dtype=gemm_dtype)
 
     def _attn(self, qkv: torch.Tensor) -> torch.Tensor:
         hpr = self.hidden_size // self.P
@@ -130,8 +136,9 @@ class LLM(nn.Module):
     def __init__(self, hidden_size: int, num_layers: int, num_heads: int, ffn_intermediate: int,
                  comm: Comm, seed: int = 0, init_std: float = 1.0, allreduce: str = "rccl",
                  allreduce_dtype: str = "bf16", attention: str = "slice", kernels: str = "hip",
-                 overlap_chunks: int = 1):
+                 overlap_chunks: int = 1, gemm_dtype: str = "bf16"):
         super().__init__()
+        self.gemm_dtype = gemm_dtype
         self.hidden_size, self.num_layers = hidden_size, num_layers
         # > 1: split the batch into this many micro-batches and interleave them so every
         # row-parallel all-reduce (on a side comm stream) runs under the next micro-batch's
@@ -153,7 +160,7 @@ class LLM(nn.Module):
         gen.manual_seed(seed + 1000 * comm.rank)
         self.layers = nn.ModuleList([
             TransformerBlock(hidden_size, num_heads, ffn_intermediate, comm, gen, init_std,
-                             allreduce, allreduce_dtype, attention, kernels)
+                             allreduce, allreduce_dtype, attention, kernels, gemm_dtype)
             for _ in range(num_layers)])
         self.ln_final = LayerNormParams(hidden_size, comm.device)
 
@@ -310,4 +317,5 @@ def create_model_from_config(config: Dict, comm: Comm) -> LLM:
                allreduce="rccl" if allreduce in ("torch",) else allreduce,
                allreduce_dtype=ex.get("allreduce_dtype", "bf16"),
                attention=ex.get("attention", "slice"), kernels=ex.get("kernels", "hip"),
-               overlap_chunks=int(ex.get("overlap_chunks", 1)))
+               overlap_chunks=int(ex.get("overlap_chunks", 1)),
+               gemm_dtype=ex.get("gemm_dtype", "bf16"))

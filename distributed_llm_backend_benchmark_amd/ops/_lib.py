@@ -80,6 +80,12 @@ _SIGS = {
     "dlbb_gemm_bf16_tn": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                   c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_int,
                                   c_int, c_void_p, c_void_p]),
+    "dlbb_quant_fp8_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_int64, c_void_p]),
+    "dlbb_gemm_fp8_nt": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                 c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                 c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "dlbb_gemm_fp8_set_bal": (None, [c_int]),
     "dlbb_gemm_set_tile": (None, [c_int]),
     "dlbb_gemm_set_stagger": (None, [c_int]),
     "dlbb_gemm_get_stagger": (c_int, []),

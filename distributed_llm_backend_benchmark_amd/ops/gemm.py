@@ -935,4 +935,6 @@ def kernel_mix() -> dict:
     out["contract_fallbacks"] = FALLBACKS["count"]
     from .norm_act import LN_FALLBACKS                # LayerNorm backward at unfused widths
     out["layernorm_bwd_fallbacks"] = LN_FALLBACKS["count"]
+    from . import fp8                                 # FP8 GEMM launches + distinct shapes
+    out["fp8"] = fp8.kernel_mix()
     return out

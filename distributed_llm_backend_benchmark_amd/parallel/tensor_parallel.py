@@ -11,7 +11,11 @@ MI355X design:
 * the row-parallel partial sum is all-reduced ON DEVICE: bf16 over RCCL by default, or the
   reference's fp32 wire format (GEMM epilogue writes fp32 directly — no cast pass), or the IPC
   one-shot/two-shot xGMI kernel; the residual add is NOT done here but fused into the next
-  LayerNorm (``ops.layernorm(x, residual=...)``).
+  LayerNorm (``ops.layernorm(x, residual=...)``);
+* ``gemm_dtype="fp8"`` (opt-in): each rank quantises its own shard — the activation per token
+  (a row-parallel input gets one scale per token PER RANK, over its H/P or F/P slice), the local
+  weight per output row, cached — and runs the FP8 GEMM (``ops.fp8``); with ``kernels="torch"``
+  the same arithmetic in torch, the model-level reference.
 """
 
 from __future__ import annotations
@@ -26,6 +30,15 @@ from .. import ops
 from .comm import Comm
 
 
+GEMM_DTYPES = ("bf16", "fp8")
+
+
+def _check_gemm_dtype(gemm_dtype: str) -> str:
+    if gemm_dtype not in GEMM_DTYPES:
+        raise ValueError(f"gemm_dtype must be one of {GEMM_DTYPES}, got {gemm_dtype!r}")
+    return gemm_dtype
+
+
 def _randn_weight(out_f: int, in_f: int, device, dtype, generator, std: float) -> nn.Parameter:
     w = torch.empty(out_f, in_f, device=device, dtype=torch.float32)
     w.normal_(0.0, std, generator=generator)
@@ -37,9 +50,10 @@ class ColumnParallelLinear(nn.Module):
 
     def __init__(self, in_features: int, out_features: int, comm: Comm,
                  dtype=torch.bfloat16, generator=None, std: float = 1.0,
-                 kernels: str = "hip"):
+                 kernels: str = "hip", gemm_dtype: str = "bf16"):
         super().__init__()
         P = comm.world_size
+        self.gemm_dtype = _check_gemm_dtype(gemm_dtype)
         if out_features % P:
             raise ValueError(f"out_features {out_features} not divisible by world {P}")
         self.in_features, self.out_features = in_features, out_features
@@ -49,6 +63,8 @@ class ColumnParallelLinear(nn.Module):
                                     generator, std)
 
     def forward(self, x: torch.Tensor, act: Optional[str] = None) -> torch.Tensor:
+        if self.gemm_dtype == "fp8":
+            return ops.fp8_linear(x, self.weight, act=act, kernels=self.kernels)
         if self.kernels == "torch":
             y = x @ self.weight.t()
             return torch.nn.functional.gelu(y) if act else y
@@ -61,9 +77,10 @@ class RowParallelLinear(nn.Module):
     def __init__(self, in_features: int, out_features: int, comm: Comm,
                  dtype=torch.bfloat16, generator=None, std: float = 1.0,
                  allreduce: str = "rccl", allreduce_dtype: str = "bf16",
-                 kernels: str = "hip"):
+                 kernels: str = "hip", gemm_dtype: str = "bf16"):
         super().__init__()
         P = comm.world_size
+        self.gemm_dtype = _check_gemm_dtype(gemm_dtype)
         if in_features % P:
             raise ValueError(f"in_features {in_features} not divisible by world {P}")
         self.comm = comm
@@ -186,8 +203,10 @@ class RowParallelLinear(nn.Module):
         per micro-batch in flight). With a registered output, ``y`` is a view of a buffer shared
         by every same-shape row-parallel layer: consume it before the next row-parallel call."""
         fp32_wire = self.allreduce_dtype == "fp32"
+        fp8 = self.gemm_dtype == "fp8"
         if self.kernels == "torch":
-            y = x @ self.weight.t()
+            y = (ops.fp8_linear(x, self.weight, kernels="torch") if fp8
+                 else x @ self.weight.t())
             if fp32_wire:
                 y = y.float()
             return self._reduce_then(y, x.dtype, None, stream, slot)
@@ -197,7 +216,12 @@ class RowParallelLinear(nn.Module):
         if reg is not None:
             buf, rid = reg
             y = buf.view(*x.shape[:-1], self.out_features)
-            ops.linear(x, self.weight, out_dtype=odt, out=y)
+            if fp8:
+                ops.fp8_linear(x, self.weight, out_dtype=odt, out=y)
+            else:
+                ops.linear(x, self.weight, out_dtype=odt, out=y)
+        elif fp8:
+            y = ops.fp8_linear(x, self.weight, out_dtype=odt)
         else:
             y = ops.linear(x, self.weight, out_dtype=odt)
         return self._reduce_then(y, x.dtype, reg, stream, slot)

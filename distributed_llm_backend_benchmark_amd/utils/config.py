@@ -19,6 +19,9 @@ Additions (all optional, defaults keep reference behaviour):
 * ``execution.kernels``: ``hip`` (hand-written gfx950 kernels) | ``torch``.
 * ``execution.overlap_chunks``: micro-batches the TP forward interleaves so each row-parallel
   all-reduce runs under another micro-batch's GEMMs (1 = the reference's blocking order).
+* ``execution.gemm_dtype``: ``bf16`` (default) | ``fp8`` — the TP linears quantise activations
+  per token and weights per output row to e4m3 and run the FP8 GEMM (``ops.fp8``); needs the
+  hidden and FFN widths of one rank's shard to be multiples of 128.
 """
 
 from __future__ import annotations
@@ -48,6 +51,7 @@ DEFAULT_CONFIG: Dict[str, Any] = {
         "attention": "slice",
         "kernels": "hip",
         "overlap_chunks": 1,
+        "gemm_dtype": "bf16",
     },
     "system": {"omp_num_threads": 14, "mkl_num_threads": 14},
 }
@@ -111,7 +115,24 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
         raise ConfigError("execution.kernels must be hip|torch")
     if not isinstance(ex["overlap_chunks"], int) or ex["overlap_chunks"] < 1:
         raise ConfigError("execution.overlap_chunks must be a positive int")
+    if ex["gemm_dtype"] not in ("bf16", "fp8"):
+        raise ConfigError(f"execution.gemm_dtype must be bf16|fp8, got {ex['gemm_dtype']!r}")
+    if ex["gemm_dtype"] == "fp8":
+        check_fp8_shapes(cfg, ws if isinstance(ws, int) else 1)
     return cfg
+
+
+def check_fp8_shapes(config: Dict[str, Any], world: int) -> None:
+    """The FP8 GEMM reduces over K-tiles of 128: the hidden size and the per-rank shard widths
+    ``hidden_size / world`` and ``ffn_intermediate / world`` (the row-parallel reductions, also
+    the column-parallel output widths) must be multiples of 128. ``world`` is the tensor-parallel
+    degree the model is cut for (``run_tp --shard-as`` passes its own)."""
+    m = config["model"]
+    for key in ("hidden_size", "ffn_intermediate"):
+        width = int(m[key])
+        if width % world or (width // world) % 128:
+            raise ConfigError(f"execution.gemm_dtype=fp8 needs model.{key} / {world} ranks to be "
+                              f"a multiple of 128, got {width} / {world}")
 
 
 def load_config(config_path: str) -> Dict[str, Any]:
