@@ -15,6 +15,12 @@ Launch (one process per GPU)::
 Differences by design: the forward is device-timed (barrier, then synchronised wall clock and
 HIP events); ``--backend`` picks the process-group backend (``rccl`` | ``gloo``) and names the
 output file; extra result keys: ``tokens_per_s``, ``tflops_per_rank``, ``allreduce_bytes``.
+
+``--decode N`` adds autoregressive decode: every timed iteration empties a per-rank KV cache,
+runs the prefill forward (timed as above) and then N one-token steps over the cache (one captured
+step replayed N times where the forward is capturable; ``--eager`` issues them from the host).
+The record gets a ``decode`` section (``ms_per_token``, ``achieved_GBps``, ...) and the file name
+the suffix ``_decode<N>``.
 """
 
 from __future__ import annotations
@@ -80,6 +86,13 @@ def parse_args(argv=None):
     ap.add_argument("--chunk-streams", action="store_true",
                     help="with --overlap-chunks: each micro-batch on a compute stream of its own "
                          "(verified concurrent, parallel/streams.py)")
+    ap.add_argument("--decode", type=int, default=None, metavar="N",
+                    help="after the prefill forward of every timed iteration, decode N tokens "
+                         "one at a time over a per-rank KV cache (execution.decode_tokens; 0 = "
+                         "the prefill forward alone); adds a \"decode\" section to the record "
+                         "and the suffix _decode<N> to the output file")
+    ap.add_argument("--max-len", type=int, default=None, metavar="L",
+                    help="with --decode: positions of the KV cache (default sequence_length + N)")
     ap.add_argument("--check-dense", action="store_true",
                     help="after warmup, load the TP shards from a dense world-1 model of the "
                          "same seed (built on every rank) and report the max error of the TP "
@@ -129,6 +142,24 @@ def main(argv=None) -> int:
         ex["benchmark_iterations"] = args.iters
     if args.output_dir:
         config["experiment"]["output_dir"] = args.output_dir
+    if args.decode is not None:
+        if args.decode < 0:
+            print("ERROR: --decode needs N >= 0")
+            return 1
+        ex["decode_tokens"] = args.decode
+    n_dec = int(ex.get("decode_tokens", 0))
+    if n_dec and ex.get("gemm_dtype", "bf16") == "fp8":
+        # the FP8 GEMM's contract at M = batch rows is not established: refuse, never fall back
+        if os.environ.get("RANK", "0") == "0":
+            print("ERROR: --decode (execution.decode_tokens) is not supported with gemm_dtype "
+                  "fp8: the FP8 GEMM is not specified for the M = batch_size rows of a decode "
+                  "step")
+        return 1
+    prompt = int(config["input"]["sequence_length"])
+    max_len = int(args.max_len) if args.max_len else prompt + n_dec
+    if n_dec and max_len < prompt + n_dec:
+        print(f"ERROR: --max-len {max_len} < sequence_length {prompt} + {n_dec} decoded tokens")
+        return 1
 
     t0 = time.perf_counter()
     cpr = config["parallelism"].get("cores_per_rank")
@@ -205,12 +236,25 @@ def main(argv=None) -> int:
     metrics.record_init_time(init_elapsed)
     gpu = comm.is_gpu
 
+    # --decode: the forward fills a KV cache (emptied before every call) and N one-token steps
+    # follow it; without it `forward` is the model itself, as before
+    cache = model.new_kv_cache(int(config["input"]["batch_size"]), max_len) if n_dec else None
+    if cache is not None:
+        cache.len_bound = prompt + n_dec        # split grid of the decode kernel: final position
+
+    def forward(x):
+        if cache is None:
+            return model(x)
+        return model(x, kv_cache=cache)
+
     fwd_bytes = 0
     for _ in range(int(ex["warmup_iterations"])):
         batch = dataset.get_batch()
         b0 = model.comm_bytes()
+        if cache is not None:
+            cache.set_length(0)
         t = time.perf_counter()
-        model(batch)
+        forward(batch)
         comm.sync()
         metrics.record_warmup_time(time.perf_counter() - t)
         fwd_bytes = model.comm_bytes() - b0
@@ -222,7 +266,7 @@ def main(argv=None) -> int:
         if rank == 0:
             print(f"dense check: {dense_check}")
 
-    run_forward = lambda: model(dataset.get_batch())  # noqa: E731
+    run_forward = lambda: forward(dataset.get_batch())  # noqa: E731
     # the timed loop replays a captured HIP graph wherever the forward is
     # capturable — the host issue cost of ~10 launches per layer (which made the eager TP
     # forward host-bound and GEMM tuning depend on the caller) is gone; --eager keeps the
@@ -243,17 +287,24 @@ def main(argv=None) -> int:
         # on any rank -> every rank runs eagerly (agreed over the host side channel BEFORE the
         # first replay, so no rank replays collectives its peers never enqueue)
         static_in = dataset.get_batch()
-        graph, err = None, None
+        graph, err, static_out = None, None, None
         try:
             side = torch.cuda.Stream(comm.device)
+            if cache is not None:
+                cache.set_length(0)
             side.wait_stream(torch.cuda.current_stream(comm.device))
             with torch.cuda.stream(side):
-                model(static_in)
+                forward(static_in)
             torch.cuda.current_stream(comm.device).wait_stream(side)
             comm.sync()
+            if cache is not None:
+                cache.set_length(0)
+                comm.sync()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                model(static_in)
+                y_cap = forward(static_in)
+                static_out = y_cap if cache is not None else None   # the decode loop's input
+                del y_cap
         except Exception as e:  # noqa: BLE001 - agreed below, then eager
             err = f"{type(e).__name__}: {e}"[:500]
             graph = None
@@ -265,9 +316,21 @@ def main(argv=None) -> int:
         else:
             graph.replay()
             comm.sync()
-            run_forward = graph.replay
+            if cache is None:
+                run_forward = graph.replay
+            else:
+                def run_forward():
+                    graph.replay()
+                    return static_out
     if graph_note and rank == 0:
         print(f"note: HIP graph replay off, running eagerly: {graph_note}")
+
+    dec = None
+    if cache is not None:
+        dec = _DecodeRunner(model, cache, comm, prompt, n_dec, dataset.get_batch(),
+                            use_graph, ex)
+        if dec.graph_note and rank == 0:
+            print(f"note: decode steps issued eagerly: {dec.graph_note}")
 
     from ..utils import tracing
 
@@ -278,12 +341,14 @@ def main(argv=None) -> int:
     ev = []
     for _ in range(int(ex["benchmark_iterations"])):
         comm.barrier()                          # reference run_mpi.py:177
+        if cache is not None:
+            cache.set_length(0)
         if gpu:
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
         t = time.perf_counter()
         with tracing.range("tp_forward"):
-            run_forward()
+            y = run_forward()
         if gpu:
             e.record()
         comm.sync()
@@ -291,6 +356,9 @@ def main(argv=None) -> int:
         metrics.record_forward_time(time.perf_counter() - t)
         if gpu:
             ev.append(s.elapsed_time(e) * 1e-3)
+        if dec is not None:
+            with tracing.range("tp_decode"):
+                dec.timed(y)
     prof.__exit__(None, None, None)
     car = getattr(model, "ipc_allreduce", lambda: None)()
     if car is not None:                 # a timed-out IPC all-reduce must not pass silently
@@ -331,7 +399,8 @@ def main(argv=None) -> int:
             "allreduce_calibration": calibration,
             "dense_check": dense_check,
             # micro-batches interleaved so all-reduces run under GEMMs (1 = blocking)
-            "overlap_chunks": model.overlap_split(
+            # (a forward that fills a KV cache runs as one micro-batch)
+            "overlap_chunks": 1 if cache is not None else model.overlap_split(
                 torch.empty(B, 1, device="meta")),
             "chunk_streams": bool(args.chunk_streams),
         }
@@ -354,6 +423,8 @@ def main(argv=None) -> int:
             "raw_metrics_rank_0": metrics.get_raw_metrics(),
             "throughput": extra,
         }
+        if dec is not None:
+            results["decode"] = dec.record()
         print_summary(summary, args.backend.upper(), rank)
         print(f"\nRank Statistics:\n  Variance across ranks: {rs['variance_across_ranks']:.6g}"
               f"\n  Coefficient of variation: {rs['coefficient_of_variation']:.4f}"
@@ -364,12 +435,160 @@ def main(argv=None) -> int:
             suffix += f"_ov{extra['overlap_chunks']}" + ("cs" if args.chunk_streams else "")
         if extra["gemm_dtype"] != "bf16":      # never overwrites the bf16 record
             suffix += f"_{extra['gemm_dtype']}"
+        if dec is not None:                    # never overwrites the prefill record
+            suffix += f"_decode{n_dec}"
+            d = results["decode"]
+            print(f"  decode: {d['ms_per_token_mean']:.4f} ms/token ({d['timing_mode']}, "
+                  f"attention {d['attention_path']}), {d['decode_tokens_per_s']:.0f} tokens/s, "
+                  f"{d['achieved_GBps']:.0f} GB/s of weights + KV")
         out = os.path.join(config["experiment"]["output_dir"],
                            f"{args.backend}_{config['experiment']['name']}{suffix}.json")
         save_results(results, out, rank)
     comm.barrier()
     comm.destroy()
     return 0
+
+
+class _DecodeRunner:
+    """The N one-token steps that follow the prefill of every timed iteration (``--decode N``).
+
+    The model has no LM head: the input of step ``i + 1`` is the last-position output of step
+    ``i`` (the final LayerNorm keeps the scale), copied into a static ``[B, 1, H]`` input on the
+    device. Two eager steps at position ``prompt`` fix the GEMM autotuner's choices for the
+    ``M = B`` shapes; then, where the forward was captured (``capturable``) and the attention
+    reads the cache length from the device (our kernel, or the stateless stub), ONE step is
+    captured at ``len_bound = prompt + N`` and replayed N times; otherwise the host issues the
+    steps. The N steps are timed by one device-event pair and by the host clock after a sync."""
+
+    def __init__(self, model, cache, comm, prompt: int, n: int, batch, capturable: bool, ex):
+        import torch
+
+        from ..ops import _lib
+        from ..ops import decode as dec_ops
+
+        self.model, self.cache, self.comm = model, cache, comm
+        self.prompt, self.n = prompt, n
+        self.gpu = comm.is_gpu
+        attention = ex.get("attention", "slice")
+        heads = model.num_heads // model.world_size
+        hd = model.hidden_size // model.num_heads
+        if attention == "slice":
+            self.attention_path = "slice"
+        elif (attention == "flash" and ex.get("kernels", "hip") != "torch" and self.gpu
+              and not _lib.force_torch() and hd in dec_ops.HEAD_DIMS):
+            self.attention_path = "hip"
+        else:
+            self.attention_path = "torch"
+        self.kv_per_key = cache.num_layers * cache.batch * heads * hd * 2 * 2   # K + V, bf16
+        self.x = torch.empty(batch.shape[0], 1, batch.shape[2], dtype=batch.dtype,
+                             device=batch.device)
+        self.dev_ms, self.host_ms = [], []
+        self.graph, self.graph_note = None, None
+
+        # warm: a prefill, then two eager steps at the first decode position
+        cache.set_length(0)
+        y = model(batch, kv_cache=cache)
+        self.x.copy_(y[:, -1:])
+        b0 = model.comm_bytes()
+        for _ in range(2):
+            cache.set_length(prompt)
+            self.step()
+        comm.sync()
+        self.allreduce_bytes_per_step = (model.comm_bytes() - b0) // 2
+        if not capturable:
+            return
+        if self.attention_path == "torch":
+            # the torch form slices the cache by the HOST position: a replay would repeat one
+            self.graph_note = "the torch decode attention is not replayable across positions"
+            return
+        graph, err = None, None
+        try:
+            side = torch.cuda.Stream(comm.device)
+            cache.set_length(prompt)
+            side.wait_stream(torch.cuda.current_stream(comm.device))
+            with torch.cuda.stream(side):
+                self.step()
+            torch.cuda.current_stream(comm.device).wait_stream(side)
+            cache.set_length(prompt)
+            comm.sync()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                self.step()
+        except Exception as e:  # noqa: BLE001 - agreed below, then eager
+            err = f"{type(e).__name__}: {e}"[:500]
+            graph = None
+        torch.cuda.synchronize(comm.device)
+        errs = _agree_host(comm, err)
+        if errs:
+            self.graph_note = f"capture failed on rank(s) {sorted(errs)}: {errs[min(errs)]}"
+            return
+        cache.set_length(prompt)
+        graph.replay()
+        comm.sync()
+        self.graph = graph
+
+    def step(self) -> None:
+        y = self.model(self.x, kv_cache=self.cache)
+        self.x.copy_(y)
+
+    def timed(self, prefill_out) -> None:
+        """N steps from the state the prefill left (cache length = prompt)."""
+        import torch
+
+        self.x.copy_(prefill_out[:, -1:])
+        # a replayed prefill advanced the device length only: bring the host mirror along
+        self.cache.set_length(self.prompt)
+        run = self.graph.replay if self.graph is not None else self.step
+        self.comm.sync()
+        if self.gpu:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+        t = time.perf_counter()
+        for _ in range(self.n):
+            run()
+        if self.gpu:
+            e.record()
+        self.comm.sync()
+        self.host_ms.append((time.perf_counter() - t) * 1e3 / self.n)
+        if self.gpu:
+            self.dev_ms.append(s.elapsed_time(e) / self.n)
+
+    def record(self) -> dict:
+        import numpy as np
+
+        from ..ops import gemm
+
+        ms = self.dev_ms or self.host_ms
+        mean = float(np.mean(ms))
+        B = self.x.shape[0]
+        # step i reads the K and V of positions [0, prompt + i] in every layer
+        kv_mean = self.kv_per_key * (self.prompt + (self.n + 1) / 2.0)
+        weights = self.model.get_memory_footprint()
+        tuned = [t for t in gemm.kernel_mix()["linear"]["tuned"] if t["key"][0] == str(B)]
+        by_choice = {}
+        for t in tuned:
+            by_choice[t["choice"]] = by_choice.get(t["choice"], 0) + 1
+        return {
+            "prompt_len": self.prompt, "new_tokens": self.n, "max_len": self.cache.max_len,
+            # per timed iteration: (time of the N steps) / N; device events on the GPU
+            "ms_per_token": [float(v) for v in ms],
+            "ms_per_token_host": [float(v) for v in self.host_ms],
+            "ms_per_token_mean": mean, "ms_per_token_p50": float(np.median(ms)),
+            "decode_tokens_per_s": B / (mean * 1e-3),
+            "kv_cache_bytes_per_rank": self.cache.nbytes,
+            "kv_bytes_read_per_step_mean": kv_mean,
+            "weight_bytes_per_rank": weights,
+            # bytes a step must read from HBM on one rank — every weight once plus the mean K / V
+            # read — over the mean step time; activations, partials and all-reduce traffic are
+            # not counted
+            "achieved_GBps": (weights + kv_mean) / (mean * 1e-3) / 1e9,
+            "allreduce_bytes_per_step": self.allreduce_bytes_per_step,
+            "attention_path": self.attention_path,
+            "timing_mode": "hip_graph_replay" if self.graph is not None else "eager",
+            "hip_graph_note": self.graph_note,
+            # the GEMM shapes of a decode step (M = batch rows) and what the autotuner runs there
+            "gemm_kernel_mix": {"shapes_by_choice": by_choice, "tuned": tuned},
+        }
 
 
 def _all_reduces_capturable(model) -> bool:

@@ -17,6 +17,8 @@ LayerNorm, so the block is ``LN1 → QKV → out-proj → AR → (add+LN2) → u
 ``overlap_chunks`` > 1 interleaves micro-batches so the all-reduces run under GEMMs (forward()).
 ``gemm_dtype="fp8"`` runs the four linears of every block through the FP8 GEMM (``ops.fp8``:
 per-token activation scales, per-output-row weight scales); the default stays bf16.
+``forward(x, kv_cache=...)`` is the autoregressive path: a prefill that fills a per-rank KV cache
+(``LLM.new_kv_cache``), then one-token decode steps over it (``ops.decode_attention``).
 """
 
 from __future__ import annotations
@@ -93,13 +95,15 @@ class TransformerBlock(nn.Module):
                                           allreduce_dtype=allreduce_dtype, kernels=kernels,
                                           gemm_dtype=gemm_dtype)
 
-    def _attn(self, qkv: torch.Tensor) -> torch.Tensor:
+    def _attn(self, qkv: torch.Tensor, cache=None, layer: int = 0) -> torch.Tensor:
         hpr = self.hidden_size // self.P
         if self.attention == "slice":
             return qkv[..., :hpr]               # reference stub, models.py:166-167 (a view)
         B, S, _ = qkv.shape
         heads = self.num_heads // self.P
         hd = hpr // heads
+        if cache is not None:
+            return self._attn_cached(qkv, heads, cache, layer)
         if self.attention == "flash" and self.kernels != "torch":
             # our causal flash kernel (csrc/attention.hip, head dim 64 / 128) straight on the
             # rank's fused [B, S, 3, heads, hd] QKV shard — no unbind / transpose copies
@@ -107,6 +111,29 @@ class TransformerBlock(nn.Module):
         q, k, v = qkv.view(B, S, 3, heads, hd).permute(2, 0, 3, 1, 4).unbind(0)
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         return o.transpose(1, 2).reshape(B, S, hpr)
+
+    def _attn_cached(self, qkv: torch.Tensor, heads: int, cache, layer: int) -> torch.Tensor:
+        """Attention with a KV cache (:class:`ops.KVCache`): ``T > 1`` = prefill of an empty
+        cache (causal attention over the prompt, K / V appended), ``T == 1`` = one decode step
+        (the token's K / V stored at ``cache.length``, attention over ``length + 1`` keys).
+        ``flash`` runs our kernels (``ops.causal_attention`` + ``ops.kv_append``,
+        ``ops.decode_attention``); ``sdpa`` and ``kernels="torch"`` the torch forms at the host
+        position. The cache is advanced by the model, not here."""
+        from ..ops import decode as dec
+
+        k, v = cache.k[layer], cache.v[layer]
+        hip = self.attention == "flash" and self.kernels != "torch"
+        if qkv.shape[1] == 1:
+            if hip:
+                return ops.decode_attention(qkv, heads, k, v, cache.length,
+                                            len_bound=cache.len_bound,
+                                            workspace=cache.workspace, pos=cache.pos)
+            return dec.torch_decode_attention(qkv, heads, k, v, cache.pos)
+        if hip:
+            ops.kv_append(qkv, heads, k, v, cache.length, pos=cache.pos)
+            return ops.causal_attention(qkv, heads)
+        dec.torch_kv_append(qkv, heads, k, v, cache.pos)
+        return self._attn(qkv)
 
     def forward(self, y1: torch.Tensor, h: torch.Tensor):
         """``y1`` = LN1(h) (computed by the caller's fused add+LN); returns (d, h) where the
@@ -118,12 +145,14 @@ class TransformerBlock(nn.Module):
         except StopIteration as e:
             return e.value
 
-    def steps(self, y1: torch.Tensor, h: torch.Tensor, slot: int = 0, stream=None):
+    def steps(self, y1: torch.Tensor, h: torch.Tensor, slot: int = 0, stream=None, cache=None,
+              layer: int = 0):
         """The block as a generator that yields after launching each of its two all-reduces
         (the event to wait on before the all-reduced tensor is read; None when inline) —
-        :meth:`LLM.forward` interleaves micro-batches on it. Returns ``(d, h)``."""
+        :meth:`LLM.forward` interleaves micro-batches on it. Returns ``(d, h)``. ``cache``: the
+        KV cache this block appends to (as layer ``layer``) and decodes from."""
         qkv = self.qkv_proj(y1)
-        a, ev = self.out_proj.launch(self._attn(qkv), slot, stream)
+        a, ev = self.out_proj.launch(self._attn(qkv, cache, layer), slot, stream)
         yield ev
         y2, h = self.ln2(a, residual=h, kernels=self.kernels)          # h = h + attn_out
         u = self.ffn_up(y2, act="gelu")                                 # GELU fused (erf)
@@ -139,6 +168,7 @@ class LLM(nn.Module):
                  overlap_chunks: int = 1, gemm_dtype: str = "bf16"):
         super().__init__()
         self.gemm_dtype = gemm_dtype
+        self.attention = attention
         self.hidden_size, self.num_layers = hidden_size, num_layers
         # > 1: split the batch into this many micro-batches and interleave them so every
         # row-parallel all-reduce (on a side comm stream) runs under the next micro-batch's
@@ -173,7 +203,16 @@ class LLM(nn.Module):
                 return car
         return None
 
-    def _micro_batch(self, x: torch.Tensor, slot: int = 0, stream=None):
+    def new_kv_cache(self, batch: int, max_len: int):
+        """A :class:`ops.KVCache` for this rank's ``num_heads / P`` local heads, ``max_len``
+        positions. ``attention="slice"`` (the stateless stub) gets one with no K / V storage:
+        decode still runs, and measures the GEMMs and the ``[B, 1, H]`` all-reduces alone."""
+        heads = self.num_heads // self.world_size
+        layers = 0 if self.attention == "slice" else self.num_layers
+        return ops.KVCache(layers, batch, heads, self.hidden_size // self.num_heads, max_len,
+                           self.comm.device)
+
+    def _micro_batch(self, x: torch.Tensor, slot: int = 0, stream=None, cache=None):
         """One micro-batch's forward as a generator over its all-reduces (see
         :meth:`TransformerBlock.steps`); returns the final LayerNorm output."""
         if not self.layers:
@@ -181,7 +220,7 @@ class LLM(nn.Module):
             return y
         y, h = self.layers[0].ln1(x, kernels=self.kernels)
         for i, layer in enumerate(self.layers):
-            d, h = yield from layer.steps(y, h, slot, stream)
+            d, h = yield from layer.steps(y, h, slot, stream, cache, i)
             nxt = self.layers[i + 1].ln1 if i + 1 < len(self.layers) else self.ln_final
             y, h = nxt(d, residual=h, kernels=self.kernels)
         return y
@@ -194,21 +233,38 @@ class LLM(nn.Module):
             return 1
         return n
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """Plain: one pass, each all-reduce inline. Overlapped (``overlap_chunks`` = n > 1): the
+    def forward(self, x: torch.Tensor, kv_cache=None) -> torch.Tensor:
+        """With ``kv_cache`` (:meth:`new_kv_cache`) and ``x [B, T, H]`` every block appends its
+        K / V: ``T > 1`` on an empty cache is the prefill, ``T == 1`` a decode step over the
+        cached tokens; ``T > 1`` on a non-empty cache raises ``ValueError`` (no chunked
+        prefill). After the final LayerNorm the cache advances by ``T`` (a device add on the
+        current stream, captured with the step). With a cache the forward runs as ONE
+        micro-batch: ``overlap_chunks`` is ignored there.
+
+        Without a cache — plain: one pass, each all-reduce inline. Overlapped (``overlap_chunks`` = n > 1): the
         batch is split into n micro-batches run round-robin, each advancing to its next
         all-reduce; the all-reduce goes to a side comm stream (normal priority: a high-priority one stretches
         every compute dispatch, profiles/r03_overlap) and the micro-batch resumes only after its compute
         stream waited for it. So all-reduce k of micro-batch A runs under the GEMMs of
         micro-batch B, and every rank issues its collectives in the same order on one comm
         stream. The reference blocks on each all-reduce (models.py:95)."""
-        n = self.overlap_split(x)
+        if kv_cache is not None:
+            T = x.shape[1]
+            if x.shape[0] != kv_cache.batch:
+                raise ValueError(f"batch {x.shape[0]} != the cache's {kv_cache.batch}")
+            if T > 1 and kv_cache.pos != 0:
+                raise ValueError(f"prefill of {T} tokens on a cache holding {kv_cache.pos}: "
+                                 "chunked prefill is not supported")
+            kv_cache.check_room(T)
+        n = 1 if kv_cache is not None else self.overlap_split(x)
         if n == 1:
-            gen = self._micro_batch(x)
+            gen = self._micro_batch(x, cache=kv_cache)
             try:
                 while True:
                     next(gen)
             except StopIteration as e:
+                if kv_cache is not None:
+                    kv_cache.advance(x.shape[1])
                 return e.value
         stream = None
         cur = torch.cuda.current_stream(x.device) if x.is_cuda else None

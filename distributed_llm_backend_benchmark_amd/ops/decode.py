@@ -1,0 +1,204 @@
+"""KV cache and single-query (decode) attention (``csrc/attn_decode.hip``).
+
+Layout, per layer and per rank: ``k_cache`` / ``v_cache`` are ``[B, H_local, L_max, D]`` bf16,
+contiguous (the key stream of one ``(b, h)`` is one contiguous run). ``length`` is ONE device
+``int32[1]`` — the tokens already cached — shared by the batch and by every layer. The kernels
+read it from device memory, so a decode step captured in a HIP graph replays for successive
+positions without recapture; the host keeps a mirror (``KVCache.pos``) for bounds checks only.
+
+* :func:`kv_append` copies the K / V rows of a fused ``[B, T, 3C]`` QKV tensor into cache
+  positions ``[length, length + T)`` (prefill: ``T = S``; decode: ``T = 1``).
+* :func:`decode_attention` takes ``qkv [B, 1, 3C]``, stores the token's K / V at ``length`` and
+  attends over ``length + 1`` keys: a split over the key axis in chunks of :data:`CHUNK` keys
+  (one workgroup per chunk, head and batch entry, fp32 partials ``(m, l, o[D])`` in a workspace)
+  and a combine kernel that merges the live chunks in chunk order and writes ``[B, 1, C]`` with
+  heads interleaved, as :func:`..attention.causal_attention` returns. No atomics: bit-identical
+  from run to run. It does NOT advance ``length``: the model does, once per step, after its
+  last layer (:meth:`KVCache.advance`).
+
+On the GPU with head dim 64 / 128 the HIP kernels are the only path (a missing library raises).
+CPU tensors, ``DLBB_KERNELS=torch`` and other head dims use torch (:func:`torch_kv_append`,
+:func:`torch_decode_attention`): an index copy into the cache and
+``F.scaled_dot_product_attention`` on ``cache[:, :, :pos + 1]``. That path slices by the HOST
+position, so it is not replayable across positions in a captured graph.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import List, Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from ._lib import check, use_hip
+from .attention import HEAD_DIMS, _views
+
+# keys per workgroup of the split kernel (csrc/attn_decode.hip takes it per launch; the
+# alternatives measured are in docs/PERFORMANCE.md)
+CHUNK = 256
+# append + attend in one launch (the chunk owning position `length` takes the token's K / V from
+# qkv and stores them) instead of a kv_append launch before the attention
+FUSED_APPEND = True
+
+
+def workspace_numel(batch: int, n_head: int, head_dim: int, max_len: int,
+                    chunk: int = CHUNK) -> int:
+    """fp32 elements of the split kernel's partials: ``[B, H, n_chunks, D + 2]``."""
+    return batch * n_head * ((max_len + chunk - 1) // chunk) * (head_dim + 2)
+
+
+class KVCache:
+    """K / V of every layer of one rank, the shared device ``length``, and the split kernel's
+    workspace. ``num_layers = 0`` holds no K / V (the stateless ``attention="slice"`` stub):
+    only the position bookkeeping."""
+
+    def __init__(self, num_layers: int, batch: int, n_head_local: int, head_dim: int,
+                 max_len: int, device, dtype=torch.bfloat16):
+        if max_len < 1 or batch < 1:
+            raise ValueError(f"KVCache needs batch >= 1 and max_len >= 1, got {batch}, {max_len}")
+        self.num_layers, self.batch = int(num_layers), int(batch)
+        self.n_head, self.head_dim, self.max_len = int(n_head_local), int(head_dim), int(max_len)
+        self.device = torch.device(device)
+        shape = (self.batch, self.n_head, self.max_len, self.head_dim)
+        self.k: List[torch.Tensor] = [torch.zeros(shape, dtype=dtype, device=self.device)
+                                      for _ in range(self.num_layers)]
+        self.v: List[torch.Tensor] = [torch.zeros(shape, dtype=dtype, device=self.device)
+                                      for _ in range(self.num_layers)]
+        self.length = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.pos = 0                    # host mirror of `length`: bounds checks only
+        # host upper bound of length + 1 for the split grid (None = max_len); a runner that
+        # replays one captured step sets the final position here before the capture
+        self.len_bound: Optional[int] = None
+        self.workspace = (torch.empty(workspace_numel(self.batch, self.n_head, self.head_dim,
+                                                      self.max_len),
+                                      dtype=torch.float32, device=self.device)
+                          if self.num_layers else None)
+
+    def set_length(self, n: int) -> None:
+        """Set the device length and the host mirror (0 = empty the cache)."""
+        if not 0 <= n <= self.max_len:
+            raise ValueError(f"KVCache length {n} outside [0, {self.max_len}]")
+        self.length.fill_(int(n))
+        self.pos = int(n)
+
+    def check_room(self, t: int) -> None:
+        if self.pos + t > self.max_len:
+            raise ValueError(f"KVCache overflow: position {self.pos} + {t} tokens > max_len "
+                             f"{self.max_len}")
+
+    def advance(self, t: int) -> None:
+        """``length += t``: a device add on the current stream (captured with the step)."""
+        self.check_room(t)
+        self.length.add_(int(t))
+        self.pos += int(t)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.k + self.v)
+
+
+def hip_supported(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
+                  v_cache: torch.Tensor) -> bool:
+    if qkv.dim() != 3 or qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
+        return False
+    C = qkv.shape[2] // 3
+    if qkv.shape[2] % 3 or C % n_head or C // n_head not in HEAD_DIMS:
+        return False
+    shape = (qkv.shape[0], n_head, k_cache.shape[2] if k_cache.dim() == 4 else -1, C // n_head)
+    return all(t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == shape
+               for t in (k_cache, v_cache))
+
+
+def _host_pos(length: torch.Tensor, pos: Optional[int]) -> int:
+    return int(length.item()) if pos is None else int(pos)
+
+
+def torch_kv_append(qkv, n_head: int, k_cache, v_cache, pos: int) -> None:
+    """Torch form of :func:`kv_append` at the host position ``pos``."""
+    T = qkv.shape[1]
+    _, k, v = _views(qkv, n_head)
+    k_cache[:, :, pos:pos + T] = k
+    v_cache[:, :, pos:pos + T] = v
+
+
+def torch_decode_attention(qkv, n_head: int, k_cache, v_cache, pos: int) -> torch.Tensor:
+    """Torch form of :func:`decode_attention` at the host position ``pos`` (not replayable
+    across positions: the slice bound is a host value)."""
+    B, _, C3 = qkv.shape
+    torch_kv_append(qkv, n_head, k_cache, v_cache, pos)
+    q, _, _ = _views(qkv, n_head)
+    o = F.scaled_dot_product_attention(q, k_cache[:, :, :pos + 1], v_cache[:, :, :pos + 1])
+    return o.transpose(1, 2).reshape(B, 1, C3 // 3)
+
+
+def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
+              length: torch.Tensor, pos: Optional[int] = None) -> None:
+    """K / V rows of ``qkv [B, T, 3C]`` -> cache positions ``[length, length + T)``. ``pos``:
+    the host's copy of ``length`` (raises before launch on overflow; None on the HIP path = no
+    host check, the kernel drops positions past the cache)."""
+    T, L_max = qkv.shape[1], k_cache.shape[2]
+    if pos is not None and pos + T > L_max:
+        raise ValueError(f"kv_append: position {pos} + {T} tokens > cache length {L_max}")
+    if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache):
+        B, _, C3 = qkv.shape
+        check(_lib.lib().dlbb_kv_append(qkv.data_ptr(), C3, k_cache.data_ptr(),
+                                        v_cache.data_ptr(), length.data_ptr(), B, T, n_head,
+                                        C3 // 3 // n_head, L_max, _lib.stream(qkv.device)),
+              "kv_append")
+        return
+    p = _host_pos(length, pos)
+    if p + T > L_max:
+        raise ValueError(f"kv_append: position {p} + {T} tokens > cache length {L_max}")
+    torch_kv_append(qkv, n_head, k_cache, v_cache, p)
+
+
+def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, length: torch.Tensor,
+                     len_bound: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
+                     pos: Optional[int] = None, chunk: Optional[int] = None,
+                     fused: Optional[bool] = None) -> torch.Tensor:
+    """One decode step of causal attention: ``qkv [B, 1, 3C]`` -> ``[B, 1, C]``; the token's
+    K / V are stored at cache position ``length`` and the query attends over ``length + 1``
+    keys. ``length`` is not advanced.
+
+    ``len_bound``: host upper bound of ``length + 1`` that sizes the split grid (default: the
+    cache length); chunks past the device length exit at once, so one captured launch serves
+    every position below the bound. ``workspace``: the cache's fp32 partials buffer
+    (:func:`workspace_numel`; allocated per call when None). ``pos``: the host's copy of
+    ``length`` for the overflow check (and the torch path). ``chunk`` / ``fused``: A/B knobs of
+    ``tools/decode_bench.py`` (defaults :data:`CHUNK`, :data:`FUSED_APPEND`)."""
+    if qkv.dim() != 3 or qkv.shape[1] != 1:
+        raise ValueError(f"decode_attention takes qkv [B, 1, 3C], got {tuple(qkv.shape)}")
+    L_max = k_cache.shape[2]
+    if pos is not None and pos + 1 > L_max:
+        raise ValueError(f"decode_attention: position {pos} + 1 > cache length {L_max}")
+    if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache):
+        B, _, C3 = qkv.shape
+        C = C3 // 3
+        D = C // n_head
+        chunk = int(chunk or CHUNK)
+        fused = FUSED_APPEND if fused is None else bool(fused)
+        bound = L_max if len_bound is None else max(1, min(int(len_bound), L_max))
+        if pos is not None and pos + 1 > bound:
+            raise ValueError(f"decode_attention: position {pos} + 1 > len_bound {bound}")
+        need = workspace_numel(B, n_head, D, bound, chunk)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
+        elif workspace.numel() < need or workspace.dtype != torch.float32:
+            raise ValueError(f"decode_attention: workspace of {workspace.numel()} fp32 < {need}")
+        out = torch.empty(B, 1, C, dtype=qkv.dtype, device=qkv.device)
+        lib, st = _lib.lib(), _lib.stream(qkv.device)
+        if not fused:
+            check(lib.dlbb_kv_append(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(),
+                                     length.data_ptr(), B, 1, n_head, D, L_max, st), "kv_append")
+        check(lib.dlbb_attn_decode(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(),
+                                   length.data_ptr(), workspace.data_ptr(), out.data_ptr(), C, B,
+                                   n_head, D, L_max, bound, chunk, int(fused),
+                                   1.0 / math.sqrt(D), st), "attn_decode")
+        return out
+    p = _host_pos(length, pos)
+    if p + 1 > L_max:
+        raise ValueError(f"decode_attention: position {p} + 1 > cache length {L_max}")
+    return torch_decode_attention(qkv, n_head, k_cache, v_cache, p)

@@ -15,7 +15,10 @@ Additions (all optional, defaults keep reference behaviour):
   native above) — the row-parallel all-reduce path.
 * ``execution.allreduce_dtype``: ``bf16`` (on-device, default) | ``fp32`` (reference wire format,
   ``models.py:84``).
-* ``execution.attention``: ``slice`` (reference stub ``models.py:162-167``) | ``sdpa``.
+* ``execution.attention``: ``slice`` (reference stub ``models.py:162-167``) | ``sdpa`` (torch
+  causal attention) | ``flash`` (our causal flash kernel; with decode, our decode kernel).
+* ``execution.decode_tokens``: after the prefill forward, decode this many tokens one at a time
+  over a KV cache (``run_tp --decode``); 0 (default) = the prefill forward alone.
 * ``execution.kernels``: ``hip`` (hand-written gfx950 kernels) | ``torch``.
 * ``execution.overlap_chunks``: micro-batches the TP forward interleaves so each row-parallel
   all-reduce runs under another micro-batch's GEMMs (1 = the reference's blocking order).
@@ -52,6 +55,7 @@ DEFAULT_CONFIG: Dict[str, Any] = {
         "kernels": "hip",
         "overlap_chunks": 1,
         "gemm_dtype": "bf16",
+        "decode_tokens": 0,
     },
     "system": {"omp_num_threads": 14, "mkl_num_threads": 14},
 }
@@ -109,8 +113,11 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
                           f"{ex['allreduce']!r}")
     if ex["allreduce_dtype"] not in ("bf16", "fp32"):
         raise ConfigError("execution.allreduce_dtype must be bf16|fp32")
-    if ex["attention"] not in ("slice", "sdpa"):
-        raise ConfigError("execution.attention must be slice|sdpa")
+    if ex["attention"] not in ("slice", "sdpa", "flash"):
+        raise ConfigError("execution.attention must be slice|sdpa|flash")
+    if not isinstance(ex["decode_tokens"], int) or isinstance(ex["decode_tokens"], bool) \
+            or ex["decode_tokens"] < 0:
+        raise ConfigError("execution.decode_tokens must be an int >= 0")
     if ex["kernels"] not in ("hip", "torch"):
         raise ConfigError("execution.kernels must be hip|torch")
     if not isinstance(ex["overlap_chunks"], int) or ex["overlap_chunks"] < 1:

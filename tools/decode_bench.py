@@ -1,0 +1,137 @@
+#!/usr/bin/env python
+"""Decode attention A/B: our split + combine kernels against torch SDPA on the same cache slice
+and against a plain device copy of the same K / V bytes (the bandwidth yardstick).
+
+For every (B, H, D, L) row all candidates are timed interleaved in ONE process: each is warmed,
+captured in a HIP graph of ``--inner`` back-to-back calls (so host launch cost is out of the
+number, as in ``run_tp``'s replayed decode step), and the graphs are replayed in alternation for
+``--rounds`` rounds; the median round is reported. Calls rotate over enough distinct caches
+that the working set exceeds the 256 MiB last-level cache (``--rotate-mb``), so small shapes are
+timed from HBM as a long-running decode would see them.
+
+Printed per candidate: microseconds per call and K / V bytes / time. The copy moves the K / V
+bytes twice (read + write), so its rate is given over 2x the bytes; ``share_of_copy`` is our
+read rate over that. ``--chunks`` adds our kernel at other split sizes, ``two_launch`` is the
+kv_append + attention form of the same step. Rows go to ``profiles/decode/attn_decode.jsonl``.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+# 7B per-rank shapes (32 heads / P for P = 1, 4, 8; head dim 128) and the GPT-2 shape
+DEFAULT_ROWS = [(8, h, 128, L) for h in (32, 8, 4) for L in (512, 2048, 8192)] + [(8, 12, 64, 1024)]
+
+
+def bench_row(B, H, D, L, args):
+    import torch
+    import torch.nn.functional as F
+
+    from distributed_llm_backend_benchmark_amd.ops import decode as dec
+
+    dev = torch.device("cuda", 0)
+    kv_bytes = 2 * B * H * L * D * 2
+    nbuf = max(1, min(16, -(-args.rotate_mb * (1 << 20) // kv_bytes)))
+    g = torch.Generator(device=dev).manual_seed(L + H)
+    caches = [torch.randn(2, B, H, L, D, generator=g, device=dev).to(torch.bfloat16)
+              for _ in range(nbuf)]
+    sink = torch.empty_like(caches[0])
+    qkv = torch.randn(B, 1, 3 * H * D, generator=g, device=dev).to(torch.bfloat16)
+    q = qkv[:, 0, :H * D].reshape(B, H, 1, D)
+    length = torch.tensor([L - 1], dtype=torch.int32, device=dev)
+    chunks = sorted(set(args.chunks))
+    ws = torch.empty(dec.workspace_numel(B, H, D, L, min(chunks + [dec.CHUNK])),
+                     dtype=torch.float32, device=dev)
+
+    def ours(i, **kw):
+        kc, vc = caches[i % nbuf]
+        return dec.decode_attention(qkv, H, kc, vc, length, workspace=ws, **kw)
+
+    def sdpa(i):
+        kc, vc = caches[i % nbuf]
+        return F.scaled_dot_product_attention(q, kc, vc)
+
+    def copy(i):
+        sink.copy_(caches[i % nbuf])
+
+    cands = {"ours": ours, "two_launch": lambda i: ours(i, fused=False), "sdpa": sdpa,
+             "copy": copy}
+    for c in chunks:
+        if c != dec.CHUNK:
+            cands[f"ours_chunk{c}"] = lambda i, c=c: ours(i, chunk=c)
+
+    graphs = {}
+    for name, fn in cands.items():                       # warm every candidate, then capture
+        for i in range(nbuf + 1):
+            fn(i)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(args.inner):
+                fn(i)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    times = {n: [] for n in graphs}
+    for _ in range(args.rounds):                         # alternate the candidates
+        for name, gr in graphs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            gr.replay()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.inner)
+    # same result from every form (the fused / two-launch / chunk variants differ by fp32
+    # reassociation only)
+    ref = sdpa(0).transpose(1, 2).reshape(B, 1, H * D).float()
+    err = float((ours(0).float() - ref).abs().max() / ref.abs().max())
+    us = {n: statistics.median(v) for n, v in times.items()}
+    row = {"B": B, "H": H, "D": D, "L": L, "kv_bytes": kv_bytes, "rotated_caches": nbuf,
+           "chunk": dec.CHUNK, "fused_append": dec.FUSED_APPEND, "inner": args.inner,
+           "rounds": args.rounds, "us": us,
+           "us_min": {n: min(v) for n, v in times.items()},
+           "GBps": {n: (2 if n == "copy" else 1) * kv_bytes / (t * 1e-6) / 1e9
+                    for n, t in us.items()},
+           "max_rel_diff_vs_sdpa": err}
+    row["share_of_copy"] = row["GBps"]["ours"] / row["GBps"]["copy"]
+    row["ours_over_sdpa"] = us["ours"] / us["sdpa"]
+    return row
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rows", nargs="*", default=None, metavar="B,H,D,L")
+    ap.add_argument("--chunks", type=int, nargs="*", default=[128, 256, 512])
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--rotate-mb", type=int, default=512)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "decode",
+                                                  "attn_decode.jsonl"))
+    args = ap.parse_args(argv)
+    rows = ([tuple(int(v) for v in r.split(",")) for r in args.rows] if args.rows
+            else DEFAULT_ROWS)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        for B, H, D, L in rows:
+            row = bench_row(B, H, D, L, args)
+            f.write(json.dumps(row) + "\n")
+            f.flush()
+            us = row["us"]
+            print(f"B={B} H={H} D={D} L={L} ({row['kv_bytes'] / 2**20:.0f} MiB K+V, "
+                  f"{row['rotated_caches']} caches): " +
+                  "  ".join(f"{n} {t:.1f} us ({row['GBps'][n]:.0f} GB/s)" for n, t in us.items())
+                  + f"  share_of_copy {row['share_of_copy']:.2f}  ours/sdpa "
+                  f"{row['ours_over_sdpa']:.2f}", flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
