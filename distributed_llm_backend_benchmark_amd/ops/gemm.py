@@ -7,7 +7,8 @@ Reference call sites: ``models.py:47`` (column-parallel) and ``models.py:81`` (r
 Dispatch: see :func:`linear` (per-shape autotune between the fused MFMA kernel and hipBLASLt +
 HIP epilogue). Shape contract of the HIP kernel: ``K % 64 == 0``, 16-byte aligned rows; M and N arbitrary.
 Shapes outside the contract are routed to ``torch.matmul`` (hipBLASLt) — a plain library GEMM —
-and counted in :data:`FALLBACKS` so benchmarks can report it.
+and counted in :data:`FALLBACKS` so benchmarks can report it. At M <= 16 (a decode step) the
+skinny-M weight-streaming kernel (``csrc/gemm_skinny.hip``) is one more autotune candidate.
 """
 
 from __future__ import annotations
@@ -367,6 +368,88 @@ def _mfma_split_linear(x2, w, bias, act, r2, out, preact):
     return out
 
 
+SKINNY_LAUNCHES = {"count": 0}    # launches of the skinny-M kernel (never its fallback)
+
+
+_SKINNY_PLANS = {}
+
+
+def skinny_plan(M: int, N: int, K: int, ncu: int):
+    """(grid, K-split inside a workgroup, K-split across workgroups, workspace bytes) of the
+    skinny-M weight-streaming GEMM (``csrc/gemm_skinny.hip`` ``dlbb_gemm_skinny_plan``) or None
+    outside its contract: 1 <= M <= 16, N % 16 == 0, K % 64 == 0."""
+    key = (int(M), int(N), int(K), int(ncu))
+    if key not in _SKINNY_PLANS:
+        out = (ctypes.c_int64 * 4)()
+        ok = _lib.lib().dlbb_gemm_skinny_plan(*key, out)
+        _SKINNY_PLANS[key] = tuple(int(v) for v in out) if ok else None
+    return _SKINNY_PLANS[key]
+
+
+def skinny_ok(x2: torch.Tensor, w: torch.Tensor, out: torch.Tensor, preact=None) -> bool:
+    """Host contract of the skinny-M candidate (checked again in C) and a valid plan: bf16
+    K-contiguous operands with 16-byte aligned rows, contiguous bf16 / fp32 output, no
+    pre-activation output (training only)."""
+    if preact is not None or x2.dim() != 2 or w.dim() != 2:
+        return False
+    M, K = x2.shape
+    N = w.shape[0]
+    if not (1 <= M <= 16) or N % 16 or K % 64 or K <= 0 or w.shape[1] != K:
+        return False
+    if not hip_supported(x2, w):
+        return False
+    if (out.dtype not in (torch.bfloat16, torch.float32) or not out.is_contiguous()
+            or tuple(out.shape) != (M, N) or out.data_ptr() % 16):
+        return False
+    ncu = _num_cus(x2.device) if x2.is_cuda else 256
+    return skinny_plan(M, N, K, ncu) is not None
+
+
+_HIP_INVALID_VALUE = 1
+
+
+def _mfma_skinny_linear(x2, w, bias, act, r2, out, preact):
+    """Skinny-M weight-streaming GEMM (``csrc/gemm_skinny.hip``): the decode step's linears,
+    M = batch rows <= 16. W goes straight from global memory to the MFMA operands, K split
+    over the waves of a workgroup and summed in a fixed order; no workspace. Outside its
+    contract: the default ping-pong (the library where that one's contract fails too).
+
+    A decode step is a chain of ~10 us launches, so the host path is kept short: only what C
+    cannot see (dtypes, unit strides, contiguity) is checked here; shape, leading dimensions
+    and alignment are checked by the C entry point, which launches nothing and returns
+    hipErrorInvalidValue outside the contract (:func:`skinny_ok` is the same contract for
+    callers that only ask)."""
+    M = x2.shape[0]
+    bf16 = torch.bfloat16
+    if (preact is None and 1 <= M <= 16 and x2.dtype == bf16 and w.dtype == bf16
+            and (out.dtype == bf16 or out.dtype == torch.float32)
+            and x2.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == x2.shape[1]
+            and out.is_contiguous()
+            and (bias is None or (bias.dtype == bf16 and bias.is_contiguous()))
+            and (r2 is None or (r2.dtype == bf16 and r2.stride(1) == 1))):
+        epi = ACTS[act]
+        if bias is not None:
+            epi |= EPI_BIAS
+        if r2 is not None:
+            epi |= EPI_RESIDUAL
+        dev = x2.device
+        rc = _lib.lib().dlbb_gemm_bf16_nt_skinny(
+            x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), M,
+            w.shape[0], x2.shape[1], _lib.ptr(bias), _lib.ptr(r2),
+            r2.stride(0) if r2 is not None else 0, epi, 1 if out.dtype == torch.float32 else 0,
+            _num_cus(dev), _lib.stream(dev))
+        if rc == 0:
+            SKINNY_LAUNCHES["count"] += 1
+            return out
+        if rc != _HIP_INVALID_VALUE:
+            check(rc, "gemm_bf16_nt_skinny")
+    if hip_supported(x2, w):
+        return _mfma_linear(x2, w, bias, act, r2, out, preact)
+    # outside every hand-written contract (K % 64, alignment): the library, as `linear`
+    return _blas_linear(x2 if x2.stride(1) == 1 else x2.contiguous(), w.contiguous(), bias,
+                        act, r2, out, preact)
+
+
 def streamk_ok(x2: torch.Tensor, w: torch.Tensor) -> bool:
     """Host contract of the Stream-K candidate (checked again in C) and a valid plan."""
     M, K = x2.shape
@@ -412,11 +495,11 @@ def _blas_linear(x2, w, bias, act, r2, out, preact):
     return out
 
 
-CHOICES = {}          # (M, N, K, epi-signature) -> "mfma" | "mfma192" | "mfma_sk" | ... | "blas"
+CHOICES = {}          # (M, N, K, epi-signature) -> "mfma" | "mfma192" | "mfma_skinny" | ... | "blas"
 CALLS = {}            # ("linear" | "wgrad", key) -> calls since import (kernel-mix accounting)
 _IMPLS = {"mfma": _mfma_linear, "mfma192": _mfma192_linear, "mfma192p": _mfma192p_linear,
           "mfma_sk": _mfma_streamk_linear, "mfma_split": _mfma_split_linear,
-          "blas": _blas_linear}
+          "mfma_skinny": _mfma_skinny_linear, "blas": _blas_linear}
 
 
 # > 0 while GEMMs share the chip with communication kernels on another stream (the overlapped
@@ -471,6 +554,10 @@ def _autotune(key, args) -> str:
     # split-K (plain bf16 products below one round of the CUs; off beside comm kernels)
     if not plain or split_plan(key[0], key[1], key[2], _num_cus(args[0].device)) is None:
         del impls["mfma_split"]
+    # skinny-M weight streaming (M <= 16: the decode step). Its grid never waits on another
+    # workgroup and assumes no co-residency, so it stays a candidate beside comm kernels.
+    if not skinny_ok(args[0], args[1], args[5], args[6]):
+        del impls["mfma_skinny"]
     times = _time_interleaved({n: (lambda f=f: f(*args)) for n, f in impls.items()})
     best, times = _choose(times, "linear", key)
     CHOICES[key] = best

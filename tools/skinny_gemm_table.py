@@ -1,0 +1,263 @@
+#!/usr/bin/env python
+"""Skinny-M GEMM table: ``mfma_skinny`` (``csrc/gemm_skinny.hip``) against every other candidate
+of the ``ops.linear`` dispatch whose contract holds (``mfma``, ``mfma_sk``, ``mfma_split``,
+``blas`` = hipBLASLt) on the decode step's shapes, and against a bandwidth floor.
+
+Rows: the eight M = 8 shapes of the 7B decode step (four at world 1, four on rank 0's shard of
+an 8-way run) plus the shard-8 QKV shape at M = 1 and M = 16.
+
+All candidates of a row are timed in ONE process, each as a HIP graph of ``--inner`` (10)
+back-to-back calls, median of ``--rounds`` (9) alternating rounds, twice:
+
+* **cold**: the calls rotate over enough distinct copies of W to exceed the 256 MiB last-level
+  cache (``--rotate-mb``; as many 10-call graphs as it takes to walk all copies, replayed in
+  turn), as the 32 layers of a decode step do;
+* **warm**: one W, as the autotuner times its candidates.
+
+The floor is ``dst.copy_(src)`` of the same W bytes. The copy moves the bytes twice (read +
+write), so its rate is given over 2x the bytes; ``share_of_copy`` is the skinny kernel's W read
+rate over that.
+
+Output in ``--out-dir`` (default ``profiles/skinny_gemm``): ``skinny_gemm.jsonl`` (one line per
+row) and ``SUMMARY.md``. ``--pmc-loop N`` instead runs N plain launches of ``mfma_skinny`` per
+row and nothing else: the form to put under ``rocprofv3 --pmc`` (counters in a run of their
+own); ``--pmc-csv FILE...`` turns such runs' counter CSVs (one per counter pass, same
+``--pmc-loop``) into ``pmc_skinny.jsonl``.
+"""
+
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+# (label, M, N, K): config/7b_config.yaml, hidden 4096, ffn 16384, batch 8
+DEFAULT_ROWS = [("w1 qkv", 8, 12288, 4096), ("w1 out", 8, 4096, 4096),
+                ("w1 up", 8, 16384, 4096), ("w1 down", 8, 4096, 16384),
+                ("s8 qkv", 8, 1536, 4096), ("s8 out", 8, 4096, 512),
+                ("s8 up", 8, 2048, 4096), ("s8 down", 8, 4096, 2048),
+                ("s8 qkv M=1", 1, 1536, 4096), ("s8 qkv M=16", 16, 1536, 4096)]
+
+
+def candidates(gemm, x, w, out):
+    M, K = x.shape
+    N = w.shape[0]
+    names = ["mfma_skinny", "mfma"]
+    if gemm.streamk_ok(x, w):
+        names.append("mfma_sk")
+    if gemm.split_plan(M, N, K, gemm._num_cus(x.device)) is not None:
+        names.append("mfma_split")
+    names.append("blas")
+    assert gemm.skinny_ok(x, w, out), "row outside the skinny contract"
+    return names
+
+
+def _graphs(torch, fn, nbuf, inner):
+    """Graphs of ``inner`` calls that together walk all ``nbuf`` weights (one graph when
+    nbuf <= inner)."""
+    for i in range(nbuf + 1):
+        fn(i)
+    torch.cuda.synchronize()
+    out = []
+    for g0 in range(0, max(nbuf, 1), inner):
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(inner):
+                fn(g0 + i)
+        gr.replay()
+        out.append(gr)
+    torch.cuda.synchronize()
+    return out
+
+
+def _time(torch, graph_sets, inner, rounds):
+    times = {n: [] for n in graph_sets}
+    for _ in range(rounds):                              # alternate the candidates
+        for name, graphs in graph_sets.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for gr in graphs:
+                gr.replay()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / (inner * len(graphs)))
+    return ({n: statistics.median(v) for n, v in times.items()},
+            {n: min(v) for n, v in times.items()})
+
+
+def bench_row(label, M, N, K, args):
+    import torch
+
+    from distributed_llm_backend_benchmark_amd.ops import gemm
+
+    dev = torch.device("cuda", 0)
+    w_bytes = N * K * 2
+    nbuf = max(1, -(-args.rotate_mb * (1 << 20) // w_bytes))
+    g = torch.Generator(device=dev).manual_seed(N + K + M)
+    ws = [(torch.rand(N, K, generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
+          for _ in range(nbuf)]
+    x = (torch.rand(M, K, generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
+    out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+    sink = torch.empty_like(ws[0])
+    names = candidates(gemm, x, ws[0], out)
+    before = gemm.SKINNY_LAUNCHES["count"]
+    ref = x.float() @ ws[0].float().t()
+    errs = {}
+    for n in names:
+        gemm._IMPLS[n](x, ws[0], None, None, None, out, None)
+        errs[n] = float((out.float() - ref).norm() / ref.norm())
+    assert gemm.SKINNY_LAUNCHES["count"] == before + 1
+
+    def call(n):
+        f = gemm._IMPLS[n]
+        return lambda i: f(x, ws[i % nbuf], None, None, None, out, None)
+
+    fns = {n: call(n) for n in names}
+    fns["copy"] = lambda i: sink.copy_(ws[i % nbuf])
+    cold = _time(torch, {n: _graphs(torch, f, nbuf, args.inner) for n, f in fns.items()},
+                 args.inner, args.rounds)
+    warm = _time(torch, {n: _graphs(torch, (lambda i, f=f: f(0)), 1, args.inner)
+                         for n, f in fns.items()}, args.inner, args.rounds)
+    del ws, sink
+    plan = gemm.skinny_plan(M, N, K, gemm._num_cus(dev))
+    row = {"row": label, "M": M, "N": N, "K": K, "w_bytes": w_bytes, "rotated_weights": nbuf,
+           "inner": args.inner, "rounds": args.rounds,
+           "plan": {"grid": plan[0], "k_split_in_workgroup": plan[1],
+                    "k_split_across_workgroups": plan[2], "workspace_bytes": plan[3]},
+           "rel_frobenius_err": {n: round(v, 6) for n, v in errs.items()}}
+    for tag, (med, mn) in (("cold", cold), ("warm", warm)):
+        others = [n for n in names if n != "mfma_skinny"]
+        best = min(others, key=lambda n: med[n])
+        row[tag] = {"us": {n: round(t, 2) for n, t in med.items()},
+                    "us_min": {n: round(t, 2) for n, t in mn.items()},
+                    "best_other": best,
+                    "skinny_over_best_other": round(med["mfma_skinny"] / med[best], 3),
+                    "fastest": min(names, key=lambda n: med[n]),
+                    "skinny_GBps": round(w_bytes / med["mfma_skinny"] / 1e3, 1),
+                    "copy_GBps_2x_bytes": round(2 * w_bytes / med["copy"] / 1e3, 1),
+                    "share_of_copy": round(med["copy"] / (2 * med["mfma_skinny"]), 3)}
+    return row
+
+
+def summary(rows) -> str:
+    cols = ["mfma_skinny", "mfma", "mfma_sk", "mfma_split", "blas", "copy"]
+    lines = ["# Skinny-M GEMM table (`tools/skinny_gemm_table.py`)", "",
+             "µs per call (HIP graph of 10 calls, median of 9 alternating rounds). cold = calls "
+             "rotate over > 256 MiB of distinct weights; warm = one weight. copy = "
+             "`dst.copy_(src)` of the W bytes (moves them twice; GB/s over 2x the bytes). "
+             "plan = workgroups x waves per workgroup (K-split inside the workgroup).", ""]
+    for tag in ("cold", "warm"):
+        lines += [f"## {tag}", "",
+                  "| row | M, N, K | W | plan | " + " | ".join(cols) +
+                  " | skinny / best other | skinny GB/s | copy GB/s | fastest |",
+                  "|" + "---|" * (len(cols) + 8)]
+        for r in rows:
+            t = r[tag]
+            us = " | ".join(f"{t['us'][c]:.1f}" if c in t["us"] else "n/a" for c in cols)
+            lines.append(
+                f"| {r['row']} | {r['M']}, {r['N']}, {r['K']} | {r['w_bytes'] / 2**20:.0f} MiB | "
+                f"{r['plan']['grid']} x {r['plan']['k_split_in_workgroup']} | {us} | "
+                f"{t['skinny_over_best_other']:.2f} ({t['best_other']}) | {t['skinny_GBps']:.0f} | "
+                f"{t['copy_GBps_2x_bytes']:.0f} | {t['fastest']} |")
+        lines.append("")
+    diff = [r["row"] for r in rows if r["cold"]["fastest"] != r["warm"]["fastest"]]
+    lines.append("Rows whose cold and warm rankings name a different fastest candidate: "
+                 + (", ".join(diff) if diff else "none") + ".")
+    return "\n".join(lines) + "\n"
+
+
+def pmc_loop(rows, n):
+    """Plain launches of the skinny kernel only (the run to put under ``rocprofv3 --pmc``)."""
+    import torch
+
+    from distributed_llm_backend_benchmark_amd.ops import gemm
+
+    dev = torch.device("cuda", 0)
+    for label, M, N, K in rows:
+        g = torch.Generator(device=dev).manual_seed(N + K + M)
+        w = (torch.rand(N, K, generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
+        x = (torch.rand(M, K, generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
+        for _ in range(n):
+            gemm._mfma_skinny_linear(x, w, None, None, None, out, None)
+        torch.cuda.synchronize()
+        print(f"pmc loop {label}: {n} launches, grid {gemm.skinny_plan(M, N, K, 256)}", flush=True)
+
+
+def pmc_csv_to_jsonl(paths, rows, n, out_path):
+    """rocprofv3 counter CSVs (one line per dispatch and counter; one file per counter pass) ->
+    one JSON line per row: the mean of every counter over that row's launches of the skinny
+    kernel (dispatch order = the order of ``pmc_loop``)."""
+    merged = [{} for _ in rows]
+    grids = [0 for _ in rows]
+    for path in paths:
+        per = {}
+        with open(path) as f:
+            for r in csv.DictReader(f):
+                if "skinny" not in r.get("Kernel_Name", ""):
+                    continue
+                d = per.setdefault(int(r["Dispatch_Id"]), {})
+                d[r["Counter_Name"]] = float(r["Counter_Value"])
+                d["_grid"] = int(r.get("Grid_Size", 0) or 0)
+        ids = sorted(per)
+        for i in range(len(rows)):
+            mine = [per[d] for d in ids[i * n:(i + 1) * n]]
+            if not mine:
+                continue
+            grids[i] = mine[0]["_grid"]
+            for k in sorted(k for k in mine[0] if k != "_grid"):
+                merged[i][k] = statistics.mean(m[k] for m in mine if k in m)
+    with open(out_path, "w") as f:
+        for (label, M, N, K), mean, grid in zip(rows, merged, grids):
+            f.write(json.dumps({"row": label, "M": M, "N": N, "K": K, "launches_per_pass": n,
+                                "grid_threads": grid, "mean": mean}) + "\n")
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rows", nargs="*", default=None, metavar="M,N,K")
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--rotate-mb", type=int, default=320)
+    ap.add_argument("--out-dir", default=os.path.join(REPO, "profiles", "skinny_gemm"))
+    ap.add_argument("--pmc-loop", type=int, default=0, metavar="N")
+    ap.add_argument("--pmc-csv", nargs="+", default=None, metavar="FILE")
+    args = ap.parse_args(argv)
+    rows = ([(r, *(int(v) for v in r.split(","))) for r in args.rows] if args.rows
+            else DEFAULT_ROWS)
+    os.makedirs(args.out_dir, exist_ok=True)
+    if args.pmc_csv:
+        pmc_csv_to_jsonl(args.pmc_csv, rows, args.pmc_loop or 5,
+                         os.path.join(args.out_dir, "pmc_skinny.jsonl"))
+        return 0
+    if args.pmc_loop:
+        pmc_loop(rows, args.pmc_loop)
+        return 0
+    done = []
+    with open(os.path.join(args.out_dir, "skinny_gemm.jsonl"), "w") as f:
+        for label, M, N, K in rows:
+            row = bench_row(label, M, N, K, args)
+            done.append(row)
+            f.write(json.dumps(row) + "\n")
+            f.flush()
+            for tag in ("cold", "warm"):
+                t = row[tag]
+                print(f"{label} [{M},{N},{K}] {tag}: " +
+                      "  ".join(f"{n} {v:.1f}" for n, v in t["us"].items()) +
+                      f" us | skinny {t['skinny_GBps']:.0f} GB/s, copy "
+                      f"{t['copy_GBps_2x_bytes']:.0f} GB/s, skinny/best other "
+                      f"{t['skinny_over_best_other']:.2f} ({t['best_other']})", flush=True)
+    with open(os.path.join(args.out_dir, "SUMMARY.md"), "w") as f:
+        f.write(summary(done))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
