@@ -20,7 +20,9 @@ output file; extra result keys: ``tokens_per_s``, ``tflops_per_rank``, ``allredu
 runs the prefill forward (timed as above) and then N one-token steps over the cache (one captured
 step replayed N times where the forward is capturable; ``--eager`` issues them from the host).
 The record gets a ``decode`` section (``ms_per_token``, ``achieved_GBps``, ...) and the file name
-the suffix ``_decode<N>``.
+the suffix ``_decode<N>``. ``--decode-weights fp8`` streams the e4m3 copy of every linear's weight
+in those steps (weight-only FP8, bf16 activations): suffix ``_decode<N>_w8``, and the ``decode``
+section counts the streamed bytes.
 """
 
 from __future__ import annotations
@@ -91,6 +93,11 @@ def parse_args(argv=None):
                          "one at a time over a per-rank KV cache (execution.decode_tokens; 0 = "
                          "the prefill forward alone); adds a \"decode\" section to the record "
                          "and the suffix _decode<N> to the output file")
+    ap.add_argument("--decode-weights", choices=["bf16", "fp8"], default=None,
+                    help="with --decode: weight type the decode steps stream "
+                         "(execution.decode_weight_dtype): fp8 = e4m3 with per-output-row scales "
+                         "on the weight-only FP8 skinny GEMM, bf16 activations, batch <= 16; "
+                         "output file gets the suffix _w8")
     ap.add_argument("--max-len", type=int, default=None, metavar="L",
                     help="with --decode: positions of the KV cache (default sequence_length + N)")
     ap.add_argument("--check-dense", action="store_true",
@@ -155,6 +162,9 @@ def main(argv=None) -> int:
                   "fp8: the FP8 GEMM is not specified for the M = batch_size rows of a decode "
                   "step")
         return 1
+    if args.decode_weights:
+        ex["decode_weight_dtype"] = args.decode_weights
+    w8 = ex.get("decode_weight_dtype", "bf16") == "fp8"
     prompt = int(config["input"]["sequence_length"])
     max_len = int(args.max_len) if args.max_len else prompt + n_dec
     if n_dec and max_len < prompt + n_dec:
@@ -188,6 +198,28 @@ def main(argv=None) -> int:
         except ConfigError as e:
             if rank == 0:
                 print(f"ERROR: {e}")
+            comm.destroy()
+            return 1
+    if w8:
+        from ..ops import _lib
+        from ..utils.config import ConfigError, check_w8_shapes
+
+        hip = comm.is_gpu and ex.get("kernels", "hip") != "torch" and not _lib.force_torch()
+        why = None
+        if not n_dec:
+            why = ("--decode-weights fp8 (execution.decode_weight_dtype) needs decode tokens "
+                   "(--decode N): only the decode steps stream the e4m3 weights")
+        elif hip and int(config["input"]["batch_size"]) > 16:
+            why = (f"--decode-weights fp8: batch_size {config['input']['batch_size']} is larger "
+                   "than the 16 rows of the W8 skinny GEMM; there is no fall-back to bf16")
+        else:
+            try:                          # with the TP degree and model overrides now known
+                check_w8_shapes(config, eff_world)
+            except ConfigError as e:
+                why = str(e)
+        if why:
+            if rank == 0:
+                print(f"ERROR: {why}")
             comm.destroy()
             return 1
     model_comm = comm
@@ -436,11 +468,13 @@ def main(argv=None) -> int:
         if extra["gemm_dtype"] != "bf16":      # never overwrites the bf16 record
             suffix += f"_{extra['gemm_dtype']}"
         if dec is not None:                    # never overwrites the prefill record
-            suffix += f"_decode{n_dec}"
+            suffix += f"_decode{n_dec}" + ("_w8" if w8 else "")
             d = results["decode"]
             print(f"  decode: {d['ms_per_token_mean']:.4f} ms/token ({d['timing_mode']}, "
                   f"attention {d['attention_path']}), {d['decode_tokens_per_s']:.0f} tokens/s, "
-                  f"{d['achieved_GBps']:.0f} GB/s of weights + KV")
+                  f"{d['achieved_GBps']:.0f} GB/s of weights + KV" +
+                  (f" ({d['weight_dtype']} weights, {d['w8_launches_per_step']} W8 launches "
+                   "per step)" if w8 else ""))
         out = os.path.join(config["experiment"]["output_dir"],
                            f"{args.backend}_{config['experiment']['name']}{suffix}.json")
         save_results(results, out, rank)
@@ -463,7 +497,7 @@ class _DecodeRunner:
     def __init__(self, model, cache, comm, prompt: int, n: int, batch, capturable: bool, ex):
         import torch
 
-        from ..ops import _lib
+        from ..ops import _lib, fp8
         from ..ops import decode as dec_ops
 
         self.model, self.cache, self.comm = model, cache, comm
@@ -489,12 +523,13 @@ class _DecodeRunner:
         cache.set_length(0)
         y = model(batch, kv_cache=cache)
         self.x.copy_(y[:, -1:])
-        b0 = model.comm_bytes()
+        b0, l0 = model.comm_bytes(), fp8.W8_LAUNCHES["count"]
         for _ in range(2):
             cache.set_length(prompt)
             self.step()
         comm.sync()
         self.allreduce_bytes_per_step = (model.comm_bytes() - b0) // 2
+        self.w8_launches_per_step = (fp8.W8_LAUNCHES["count"] - l0) // 2
         if not capturable:
             return
         if self.attention_path == "torch":
@@ -564,11 +599,13 @@ class _DecodeRunner:
         # step i reads the K and V of positions [0, prompt + i] in every layer
         kv_mean = self.kv_per_key * (self.prompt + (self.n + 1) / 2.0)
         weights = self.model.get_memory_footprint()
+        w8 = self.model.decode_weight_dtype == "fp8"
+        streamed = self.model.decode_weight_bytes()    # == weights unless the steps stream e4m3
         tuned = [t for t in gemm.kernel_mix()["linear"]["tuned"] if t["key"][0] == str(B)]
         by_choice = {}
         for t in tuned:
             by_choice[t["choice"]] = by_choice.get(t["choice"], 0) + 1
-        return {
+        rec = {
             "prompt_len": self.prompt, "new_tokens": self.n, "max_len": self.cache.max_len,
             # per timed iteration: (time of the N steps) / N; device events on the GPU
             "ms_per_token": [float(v) for v in ms],
@@ -581,14 +618,21 @@ class _DecodeRunner:
             # bytes a step must read from HBM on one rank — every weight once plus the mean K / V
             # read — over the mean step time; activations, partials and all-reduce traffic are
             # not counted
-            "achieved_GBps": (weights + kv_mean) / (mean * 1e-3) / 1e9,
+            "achieved_GBps": (streamed + kv_mean) / (mean * 1e-3) / 1e9,
             "allreduce_bytes_per_step": self.allreduce_bytes_per_step,
             "attention_path": self.attention_path,
             "timing_mode": "hip_graph_replay" if self.graph is not None else "eager",
             "hip_graph_note": self.graph_note,
             # the GEMM shapes of a decode step (M = batch rows) and what the autotuner runs there
             "gemm_kernel_mix": {"shapes_by_choice": by_choice, "tuned": tuned},
+            "weight_dtype": self.model.decode_weight_dtype,
         }
+        if w8:
+            # the e4m3 bytes and row scales of every linear (+ the LayerNorm parameters): what a
+            # step streams; weight_bytes_per_rank stays the resident bf16 footprint
+            rec["weight_stream_bytes_per_rank"] = streamed
+            rec["w8_launches_per_step"] = self.w8_launches_per_step
+        return rec
 
 
 def _all_reduces_capturable(model) -> bool:
@@ -644,8 +688,12 @@ def _check_against_dense(config, comm, model, batch) -> dict:
     rel = max(errs) / max(scale, 1e-30)
     # fp8: the dense model quantises a row-parallel input with one scale per token, the TP model
     # with one per token and rank, so the two differ by e4m3 rounding (2^-4 per element) carried
-    # through every layer, not by bf16 rounding
-    tol = 0.25 if config["execution"].get("gemm_dtype", "bf16") == "fp8" else 5e-2
+    # through every layer, not by bf16 rounding. decode_weight_dtype=fp8 gets the same tolerance:
+    # wherever it applies the weights carry the same e4m3 rounding (the forwards compared here
+    # have no KV cache, so they run on the bf16 weights and sit far inside it)
+    exe = config["execution"]
+    fp8 = "fp8" in (exe.get("gemm_dtype", "bf16"), exe.get("decode_weight_dtype", "bf16"))
+    tol = 0.25 if fp8 else 5e-2
     return {"max_abs_err": max(errs), "ref_max_abs": scale, "rel_err": rel, "tolerance": tol,
             "passed": bool(rel < tol and all(e == e for e in errs))}
 

@@ -19,6 +19,9 @@ LayerNorm, so the block is ``LN1 → QKV → out-proj → AR → (add+LN2) → u
 per-token activation scales, per-output-row weight scales); the default stays bf16.
 ``forward(x, kv_cache=...)`` is the autoregressive path: a prefill that fills a per-rank KV cache
 (``LLM.new_kv_cache``), then one-token decode steps over it (``ops.decode_attention``).
+``decode_weight_dtype="fp8"`` (opt-in) streams the e4m3 copy of every linear's weight in those
+decode steps (``ops.w8_linear``, bf16 activations); prefill and cache-less forwards keep the bf16
+weights. Both copies are resident: + 50 % weight memory.
 """
 
 from __future__ import annotations
@@ -33,7 +36,8 @@ from .. import ops
 from ..ops import gemm as gemm_ops
 from ..parallel.comm import Comm
 from ..parallel.streams import concurrent_stream
-from ..parallel.tensor_parallel import ColumnParallelLinear, RowParallelLinear
+from ..parallel.tensor_parallel import (ColumnParallelLinear, RowParallelLinear,
+                                        _check_decode_weight_dtype)
 
 MODEL_CONFIGS: Dict[str, Dict[str, int]] = {
     "1B": {"hidden_size": 2048, "num_layers": 24, "num_heads": 16, "ffn_intermediate": 8192},
@@ -71,7 +75,8 @@ class TransformerBlock(nn.Module):
     def __init__(self, hidden_size: int, num_heads: int, ffn_intermediate: int, comm: Comm,
                  generator=None, init_std: float = 1.0, allreduce: str = "rccl",
                  allreduce_dtype: str = "bf16", attention: str = "slice",
-                 kernels: str = "hip", gemm_dtype: str = "bf16"):
+                 kernels: str = "hip", gemm_dtype: str = "bf16",
+                 decode_weight_dtype: str = "bf16"):
         super().__init__()
         P = comm.world_size
         self.hidden_size, self.num_heads, self.P = hidden_size, num_heads, P
@@ -81,19 +86,23 @@ class TransformerBlock(nn.Module):
         self.ln1 = LayerNormParams(hidden_size, dev)
         self.qkv_proj = ColumnParallelLinear(hidden_size, 3 * hidden_size, comm,
                                              generator=generator, std=init_std, kernels=kernels,
-                                             gemm_dtype=gemm_dtype)
+                                             gemm_dtype=gemm_dtype,
+                                             decode_weight_dtype=decode_weight_dtype)
         self.out_proj = RowParallelLinear(hidden_size, hidden_size, comm, generator=generator,
                                           std=init_std, allreduce=allreduce,
                                           allreduce_dtype=allreduce_dtype, kernels=kernels,
-                                          gemm_dtype=gemm_dtype)
+                                          gemm_dtype=gemm_dtype,
+                                          decode_weight_dtype=decode_weight_dtype)
         self.ln2 = LayerNormParams(hidden_size, dev)
         self.ffn_up = ColumnParallelLinear(hidden_size, ffn_intermediate, comm,
                                            generator=generator, std=init_std, kernels=kernels,
-                                           gemm_dtype=gemm_dtype)
+                                           gemm_dtype=gemm_dtype,
+                                           decode_weight_dtype=decode_weight_dtype)
         self.ffn_down = RowParallelLinear(ffn_intermediate, hidden_size, comm,
                                           generator=generator, std=init_std, allreduce=allreduce,
                                           allreduce_dtype=allreduce_dtype, kernels=kernels,
-                                          gemm_dtype=gemm_dtype)
+                                          gemm_dtype=gemm_dtype,
+                                          decode_weight_dtype=decode_weight_dtype)
 
     def _attn(self, qkv: torch.Tensor, cache=None, layer: int = 0) -> torch.Tensor:
         hpr = self.hidden_size // self.P
@@ -150,13 +159,15 @@ class TransformerBlock(nn.Module):
         """The block as a generator that yields after launching each of its two all-reduces
         (the event to wait on before the all-reduced tensor is read; None when inline) —
         :meth:`LLM.forward` interleaves micro-batches on it. Returns ``(d, h)``. ``cache``: the
-        KV cache this block appends to (as layer ``layer``) and decodes from."""
-        qkv = self.qkv_proj(y1)
-        a, ev = self.out_proj.launch(self._attn(qkv, cache, layer), slot, stream)
+        KV cache this block appends to (as layer ``layer``) and decodes from. A one-token step
+        over a cache is a decode step: its four linears are told so (``decode_weight_dtype``)."""
+        decode = cache is not None and y1.shape[1] == 1
+        qkv = self.qkv_proj(y1, decode=decode)
+        a, ev = self.out_proj.launch(self._attn(qkv, cache, layer), slot, stream, decode=decode)
         yield ev
         y2, h = self.ln2(a, residual=h, kernels=self.kernels)          # h = h + attn_out
-        u = self.ffn_up(y2, act="gelu")                                 # GELU fused (erf)
-        d, ev = self.ffn_down.launch(u, slot, stream)
+        u = self.ffn_up(y2, act="gelu", decode=decode)                  # GELU fused (erf)
+        d, ev = self.ffn_down.launch(u, slot, stream, decode=decode)
         yield ev
         return d, h
 
@@ -165,9 +176,11 @@ class LLM(nn.Module):
     def __init__(self, hidden_size: int, num_layers: int, num_heads: int, ffn_intermediate: int,
                  comm: Comm, seed: int = 0, init_std: float = 1.0, allreduce: str = "rccl",
                  allreduce_dtype: str = "bf16", attention: str = "slice", kernels: str = "hip",
-                 overlap_chunks: int = 1, gemm_dtype: str = "bf16"):
+                 overlap_chunks: int = 1, gemm_dtype: str = "bf16",
+                 decode_weight_dtype: str = "bf16"):
         super().__init__()
         self.gemm_dtype = gemm_dtype
+        self.decode_weight_dtype = _check_decode_weight_dtype(decode_weight_dtype, gemm_dtype)
         self.attention = attention
         self.hidden_size, self.num_layers = hidden_size, num_layers
         # > 1: split the batch into this many micro-batches and interleave them so every
@@ -190,7 +203,8 @@ class LLM(nn.Module):
         gen.manual_seed(seed + 1000 * comm.rank)
         self.layers = nn.ModuleList([
             TransformerBlock(hidden_size, num_heads, ffn_intermediate, comm, gen, init_std,
-                             allreduce, allreduce_dtype, attention, kernels, gemm_dtype)
+                             allreduce, allreduce_dtype, attention, kernels, gemm_dtype,
+                             decode_weight_dtype)
             for _ in range(num_layers)])
         self.ln_final = LayerNormParams(hidden_size, comm.device)
 
@@ -206,7 +220,13 @@ class LLM(nn.Module):
     def new_kv_cache(self, batch: int, max_len: int):
         """A :class:`ops.KVCache` for this rank's ``num_heads / P`` local heads, ``max_len``
         positions. ``attention="slice"`` (the stateless stub) gets one with no K / V storage:
-        decode still runs, and measures the GEMMs and the ``[B, 1, H]`` all-reduces alone."""
+        decode still runs, and measures the GEMMs and the ``[B, 1, H]`` all-reduces alone.
+        With ``decode_weight_dtype="fp8"`` on the HIP path the batch is the M of the W8 skinny
+        GEMM: more than 16 rows raise here, not in the middle of a step."""
+        if (self.decode_weight_dtype == "fp8" and batch > 16 and self.kernels != "torch"
+                and self.comm.device.type == "cuda" and not ops._lib.force_torch()):
+            raise ValueError(f"decode_weight_dtype='fp8': batch {batch} is larger than the 16 "
+                             "rows of the W8 skinny GEMM; there is no fall-back to bf16")
         heads = self.num_heads // self.world_size
         layers = 0 if self.attention == "slice" else self.num_layers
         return ops.KVCache(layers, batch, heads, self.hidden_size // self.num_heads, max_len,
@@ -344,6 +364,21 @@ class LLM(nn.Module):
     def get_memory_footprint(self) -> int:
         return sum(p.numel() * p.element_size() for p in self.parameters())
 
+    def decode_weight_bytes(self) -> int:
+        """Parameter bytes one decode step streams on this rank. ``decode_weight_dtype="fp8"``:
+        every linear's N x K e4m3 bytes and its N fp32 row scales, plus the LayerNorm
+        parameters; ``"bf16"``: :meth:`get_memory_footprint`."""
+        if self.decode_weight_dtype != "fp8":
+            return self.get_memory_footprint()
+        total = 0
+        for m in self.modules():
+            if isinstance(m, (ColumnParallelLinear, RowParallelLinear)):
+                n, k = m.weight.shape
+                total += n * k + 4 * n
+            elif isinstance(m, LayerNormParams):
+                total += sum(p.numel() * p.element_size() for p in m.parameters())
+        return total
+
     def comm_bytes(self) -> int:
         return sum(m.comm_bytes for m in self.modules() if isinstance(m, RowParallelLinear))
 
@@ -374,4 +409,5 @@ def create_model_from_config(config: Dict, comm: Comm) -> LLM:
                allreduce_dtype=ex.get("allreduce_dtype", "bf16"),
                attention=ex.get("attention", "slice"), kernels=ex.get("kernels", "hip"),
                overlap_chunks=int(ex.get("overlap_chunks", 1)),
-               gemm_dtype=ex.get("gemm_dtype", "bf16"))
+               gemm_dtype=ex.get("gemm_dtype", "bf16"),
+               decode_weight_dtype=ex.get("decode_weight_dtype", "bf16"))

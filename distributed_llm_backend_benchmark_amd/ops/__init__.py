@@ -3,7 +3,8 @@
 * :mod:`.elementwise` — n-way sum-reduce, cast, strided pack, multi-tensor chunk copy
   (flatten/unflatten/all-to-all packing).
 * :mod:`.gemm` — MFMA bf16 GEMM with fused bias / GELU / residual epilogues.
-* :mod:`.fp8` — e4m3 row quantiser and FP8 GEMM (block-scaled MFMA), the opt-in FP8 TP forward.
+* :mod:`.fp8` — e4m3 row quantiser and FP8 GEMM (block-scaled MFMA), the opt-in FP8 TP forward;
+  the weight-only FP8 (W8A16) skinny GEMM of the opt-in FP8-weight decode step.
 * :mod:`.norm_act` — fused residual+LayerNorm and bias+GELU (fwd + bwd, autograd).
 * :mod:`.optim` — flat fused AdamW.
 * :mod:`.xent` — fused softmax cross-entropy on bf16 logits; LM-head-fused linear + loss.
@@ -16,7 +17,7 @@ from . import _lib
 from ._lib import available, loaded_path, KernelError
 from .elementwise import reduce_sum, cast, pack_rows, ChunkTable, ScaleTable, flatten_into
 from .gemm import linear
-from .fp8 import quantize_rows, linear_fp8, fp8_linear
+from .fp8 import quantize_rows, linear_fp8, fp8_linear, linear_w8, w8_linear, W8_LAUNCHES
 from .norm_act import layernorm, bias_gelu
 from .optim import FlatAdamW
 from .xent import cross_entropy, linear_cross_entropy
@@ -27,4 +28,4 @@ from .embedding import embedding
 __all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
            "ChunkTable", "ScaleTable", "flatten_into", "linear", "layernorm", "bias_gelu",
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
-           "linear_fp8", "fp8_linear"]
+           "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES"]

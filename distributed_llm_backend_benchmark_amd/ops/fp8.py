@@ -18,10 +18,17 @@ The path is opt-in (``gemm_dtype="fp8"`` on the TP layers / ``execution.gemm_dty
 GEMMs are untouched. On a GPU tensor the HIP kernels are the only implementation: a shape outside
 the kernel contract raises, there is no fall-back to bf16. The torch formulas below serve CPU
 tensors, ``DLBB_KERNELS=torch`` and ``kernels="torch"`` (the model-level reference).
+
+Weight-only FP8 for the decode step (``csrc/gemm_skinny_w8.hip``, :func:`linear_w8` /
+:func:`w8_linear`): at M = batch rows <= 16 a linear is a pure stream of its weight, so the e4m3
+copy of the weight (the same cached ``quantize_weight`` entry) is streamed instead — half the
+bytes — widened to bf16 in registers (exact) and multiplied with the bf16 activation as it is;
+the row scale is applied to the fp32 accumulator. Opt-in too (``decode_weight_dtype="fp8"``).
 """
 
 from __future__ import annotations
 
+import ctypes
 import weakref
 from typing import Optional, Tuple
 
@@ -30,7 +37,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, use_hip
-from .gemm import ACTS, EPI_BIAS, EPI_RESIDUAL
+from .gemm import ACTS, EPI_BIAS, EPI_RESIDUAL, _HIP_INVALID_VALUE, _num_cus
 
 E4M3 = torch.float8_e4m3fn
 E4M3_MAX = 448.0
@@ -283,6 +290,144 @@ def fp8_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
     wq, ws = quantize_weight(w, kernels)
     xq, xs = quantize_rows(x, kernels=kernels)
     return linear_fp8(xq, xs, wq, ws, bias, act, residual, out_dtype, out, kernels=kernels)
+
+
+# ---- weight-only FP8 (W8A16) for the decode step: csrc/gemm_skinny_w8.hip ----------------------
+
+W8_LAUNCHES = {"count": 0}     # launches of the W8 skinny kernel itself
+
+_W8_CONTRACT = "contract: 1 <= M <= 16, N % 16 == 0, K % 64 == 0; there is no fall-back to bf16"
+_W8_PLANS = {}
+
+
+def w8_contract_error(M: int, N: int, K: int) -> Optional[str]:
+    """Why (M, N, K) is outside the W8 skinny GEMM's shape contract, or None."""
+    if M <= 0 or N <= 0 or K <= 0:
+        return "empty operand"
+    if M > 16:
+        return f"M = {M} is larger than 16"
+    if N % 16:
+        return f"N = {N} is not a multiple of 16"
+    if K % 64:
+        return f"K = {K} is not a multiple of 64"
+    return None
+
+
+def w8_skinny_plan(M: int, N: int, K: int, ncu: int):
+    """(grid, K-split inside a workgroup, K-split across workgroups, workspace bytes) of the W8
+    skinny GEMM (``dlbb_gemm_w8_skinny_plan``), or None outside its shape contract."""
+    key = (int(M), int(N), int(K), int(ncu))
+    if key not in _W8_PLANS:
+        out = (ctypes.c_int64 * 4)()
+        ok = _lib.lib().dlbb_gemm_w8_skinny_plan(*key, out)
+        _W8_PLANS[key] = tuple(int(v) for v in out) if ok else None
+    return _W8_PLANS[key]
+
+
+def _w8_refusal(x2, wq, ws1, out, M, N, K) -> str:
+    """Names the term of the C contract a refused call violated (the slow path of a refusal)."""
+    why = w8_contract_error(M, N, K)
+    if why:
+        return why
+    if M > 1 and (x2.stride(0) % 8 or x2.stride(0) < K):
+        return f"x row stride {x2.stride(0)} is not a multiple of 8 elements >= K"
+    if N > 1 and (wq.stride(0) % 16 or wq.stride(0) < K):
+        return f"wq row stride {wq.stride(0)} is not a multiple of 16 bytes >= K"
+    for name, t in (("x", x2), ("wq", wq), ("ws", ws1), ("out", out)):
+        if t.data_ptr() % 16:
+            return f"{name} is not 16-byte aligned"
+    return "refused by the kernel's entry point"
+
+
+def linear_w8(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor,
+              bias: Optional[torch.Tensor] = None, act: Optional[str] = None,
+              residual: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.bfloat16,
+              out: Optional[torch.Tensor] = None, kernels: Optional[str] = None) -> torch.Tensor:
+    """``act((x @ wq.float().T) * ws[None, :] + bias) + residual``: weight-only FP8 for the
+    M = batch rows of a decode step. ``x [..., K]`` bf16, ``wq [N, K]`` e4m3fn (K-contiguous),
+    ``ws [N]`` fp32 row scales (:func:`quantize_rows`), ``bias [N]`` / ``residual [..., N]`` bf16;
+    fp32 accumulation, bf16 or fp32 result ``[..., N]``.
+
+    HIP contract: ``1 <= M <= 16`` (M = rows of ``x``), ``N % 16 == 0``, ``K % 64 == 0``, 16-byte
+    aligned rows of ``x`` and ``wq``. Anything else raises ``ValueError`` before any launch.
+
+    The host path is short (a decode step is a chain of ~10 us launches): dtypes and unit strides
+    are checked here, shape, leading dimensions and alignment by the C entry point, which
+    launches nothing outside the contract; only then is the violated term worked out."""
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    K = x.shape[-1]
+    N = wq.shape[0]
+    if wq.dim() != 2 or wq.shape[1] != K:
+        raise ValueError(f"linear_w8: x[..., {K}] vs wq{tuple(wq.shape)}")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("linear_w8: out_dtype must be bf16 or fp32")
+    lead = x.shape[:-1]
+    x2 = x if x.dim() == 2 else x.reshape(-1, K)
+    M = x2.shape[0]
+    if ws.numel() != N:
+        raise ValueError("linear_w8: one scale per row of wq")
+    if not _want_hip(kernels, x, wq):
+        y = (x2.float() @ wq.float().t()) * ws.reshape(1, N).float()
+        y = _epilogue_torch(y, bias, act, None if residual is None else residual.reshape(M, N),
+                            out_dtype).reshape(*lead, N)
+        return y if out is None else out.copy_(y.reshape(out.shape))
+    if x.dtype != torch.bfloat16 or wq.dtype != E4M3 or ws.dtype != torch.float32:
+        raise ValueError(f"linear_w8: x must be bf16, wq {E4M3}, ws fp32; got {x.dtype} / "
+                         f"{wq.dtype} / {ws.dtype}")
+    if x2.stride(1) != 1 or wq.stride(1) != 1:
+        raise ValueError("linear_w8: operands must be K-contiguous")
+    ws1 = ws if ws.dim() == 1 else ws.reshape(N)
+    if not ws1.is_contiguous():
+        raise ValueError("linear_w8: ws must be contiguous")
+    if out is None:
+        out = torch.empty(*lead, N, dtype=out_dtype, device=x.device)
+    elif out.dtype not in (torch.bfloat16, torch.float32) or not out.is_contiguous() \
+            or out.numel() != M * N:
+        raise ValueError("linear_w8: out must be contiguous bf16/fp32 [..., N]")
+    epi = ACTS[act]
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or bias.numel() != N or not bias.is_contiguous():
+            raise ValueError("linear_w8: bias must be contiguous bf16 [N]")
+        epi |= EPI_BIAS
+    r2 = None
+    if residual is not None:
+        r2 = residual.reshape(M, N)
+        if r2.dtype != torch.bfloat16 or r2.stride(1) != 1:
+            r2 = r2.to(torch.bfloat16).contiguous()
+        epi |= EPI_RESIDUAL
+    dev = x.device
+    rc = _lib.lib().dlbb_gemm_w8_nt_skinny(
+        x2.data_ptr(), x2.stride(0) if M > 1 else K, wq.data_ptr(),
+        wq.stride(0) if N > 1 else K, ws1.data_ptr(), out.data_ptr(), M, N, K, _lib.ptr(bias),
+        _lib.ptr(r2), r2.stride(0) if r2 is not None else 0, epi,
+        1 if out.dtype == torch.float32 else 0, _num_cus(dev), _lib.stream(dev))
+    if rc == 0:
+        W8_LAUNCHES["count"] += 1
+        return out
+    if rc == _HIP_INVALID_VALUE:
+        raise ValueError(f"linear_w8: {_w8_refusal(x2, wq, ws1, out, M, N, K)} ({_W8_CONTRACT})")
+    check(rc, "gemm_w8_nt_skinny")
+
+
+def w8_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+              act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
+              out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
+              kernels: Optional[str] = None) -> torch.Tensor:
+    """``act(x @ w.T + bias) + residual`` with the bf16 weight ``w [N, K]`` streamed as e4m3:
+    quantised per output row once (:func:`quantize_weight`, the cache entry :func:`fp8_linear`
+    uses; before any graph capture), the bf16 activation ``x [..., K]`` as it is."""
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16
+    if w.shape[1] != x.shape[-1]:
+        raise ValueError(f"w8_linear: x[..., {x.shape[-1]}] vs w{tuple(w.shape)}")
+    if _want_hip(kernels, x, w):            # refuse before the quantiser launches anything
+        M = x.numel() // max(x.shape[-1], 1)
+        why = w8_contract_error(M, w.shape[0], x.shape[-1])
+        if why:
+            raise ValueError(f"w8_linear: {why} ({_W8_CONTRACT})")
+    wq, ws = quantize_weight(w, kernels)
+    return linear_w8(x, wq, ws, bias, act, residual, out_dtype, out, kernels=kernels)
 
 
 def kernel_mix() -> dict:

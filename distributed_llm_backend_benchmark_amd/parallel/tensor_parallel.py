@@ -15,7 +15,11 @@ MI355X design:
 * ``gemm_dtype="fp8"`` (opt-in): each rank quantises its own shard — the activation per token
   (a row-parallel input gets one scale per token PER RANK, over its H/P or F/P slice), the local
   weight per output row, cached — and runs the FP8 GEMM (``ops.fp8``); with ``kernels="torch"``
-  the same arithmetic in torch, the model-level reference.
+  the same arithmetic in torch, the model-level reference;
+* ``decode_weight_dtype="fp8"`` (opt-in): a call flagged ``decode=True`` (a one-token step over
+  a KV cache, M = batch rows) streams the e4m3 copy of the local weight through the weight-only
+  FP8 skinny GEMM (``ops.w8_linear``: bf16 activation, row scale on the fp32 accumulator); every
+  other call keeps the bf16 weight and today's dispatch. Both copies of the weight are resident.
 """
 
 from __future__ import annotations
@@ -39,6 +43,16 @@ def _check_gemm_dtype(gemm_dtype: str) -> str:
     return gemm_dtype
 
 
+def _check_decode_weight_dtype(decode_weight_dtype: str, gemm_dtype: str) -> str:
+    if decode_weight_dtype not in GEMM_DTYPES:
+        raise ValueError(f"decode_weight_dtype must be one of {GEMM_DTYPES}, got "
+                         f"{decode_weight_dtype!r}")
+    if decode_weight_dtype == "fp8" and gemm_dtype == "fp8":
+        raise ValueError("decode_weight_dtype='fp8' cannot be combined with gemm_dtype='fp8' "
+                         "(the FP8 GEMM is not specified for the rows of a decode step)")
+    return decode_weight_dtype
+
+
 def _randn_weight(out_f: int, in_f: int, device, dtype, generator, std: float) -> nn.Parameter:
     w = torch.empty(out_f, in_f, device=device, dtype=torch.float32)
     w.normal_(0.0, std, generator=generator)
@@ -50,10 +64,12 @@ class ColumnParallelLinear(nn.Module):
 
     def __init__(self, in_features: int, out_features: int, comm: Comm,
                  dtype=torch.bfloat16, generator=None, std: float = 1.0,
-                 kernels: str = "hip", gemm_dtype: str = "bf16"):
+                 kernels: str = "hip", gemm_dtype: str = "bf16",
+                 decode_weight_dtype: str = "bf16"):
         super().__init__()
         P = comm.world_size
         self.gemm_dtype = _check_gemm_dtype(gemm_dtype)
+        self.decode_weight_dtype = _check_decode_weight_dtype(decode_weight_dtype, gemm_dtype)
         if out_features % P:
             raise ValueError(f"out_features {out_features} not divisible by world {P}")
         self.in_features, self.out_features = in_features, out_features
@@ -62,7 +78,10 @@ class ColumnParallelLinear(nn.Module):
         self.weight = _randn_weight(self.out_per_rank, in_features, comm.device, dtype,
                                     generator, std)
 
-    def forward(self, x: torch.Tensor, act: Optional[str] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, act: Optional[str] = None,
+                decode: bool = False) -> torch.Tensor:
+        if decode and self.decode_weight_dtype == "fp8":
+            return ops.w8_linear(x, self.weight, act=act, kernels=self.kernels)
         if self.gemm_dtype == "fp8":
             return ops.fp8_linear(x, self.weight, act=act, kernels=self.kernels)
         if self.kernels == "torch":
@@ -77,10 +96,12 @@ class RowParallelLinear(nn.Module):
     def __init__(self, in_features: int, out_features: int, comm: Comm,
                  dtype=torch.bfloat16, generator=None, std: float = 1.0,
                  allreduce: str = "rccl", allreduce_dtype: str = "bf16",
-                 kernels: str = "hip", gemm_dtype: str = "bf16"):
+                 kernels: str = "hip", gemm_dtype: str = "bf16",
+                 decode_weight_dtype: str = "bf16"):
         super().__init__()
         P = comm.world_size
         self.gemm_dtype = _check_gemm_dtype(gemm_dtype)
+        self.decode_weight_dtype = _check_decode_weight_dtype(decode_weight_dtype, gemm_dtype)
         if in_features % P:
             raise ValueError(f"in_features {in_features} not divisible by world {P}")
         self.comm = comm
@@ -173,12 +194,12 @@ class RowParallelLinear(nn.Module):
         else:
             dist.all_reduce(t)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, decode: bool = False) -> torch.Tensor:
         """Public API: always an OWNED tensor. (The zero-copy :meth:`launch` may return a view
         of the IPC-registered output buffer, which every same-shape row-parallel layer shares and
         the next call rewrites — ADVICE r03; only the model's block, which consumes each output
         in the next LayerNorm, uses that path.)"""
-        y, _ = self.launch(x)
+        y, _ = self.launch(x, decode=decode)
         if self._aliases_registered(y):
             y = y.clone()
         return y
@@ -194,18 +215,22 @@ class RowParallelLinear(nn.Module):
                 return True
         return False
 
-    def launch(self, x: torch.Tensor, slot: int = 0, stream=None):
+    def launch(self, x: torch.Tensor, slot: int = 0, stream=None, decode: bool = False):
         """Internal zero-copy path (TransformerBlock): GEMM on the current stream, then the
         all-reduce — on ``stream`` when given (a
         side comm stream: returns ``(y, event)``, and the caller makes its stream wait on the
         event before reading ``y``; the overlapped TP forward runs another micro-batch's GEMMs
         meanwhile), else inline (``event`` None). ``slot``: which registered output buffer (one
         per micro-batch in flight). With a registered output, ``y`` is a view of a buffer shared
-        by every same-shape row-parallel layer: consume it before the next row-parallel call."""
+        by every same-shape row-parallel layer: consume it before the next row-parallel call.
+        ``decode``: a one-token step; with ``decode_weight_dtype="fp8"`` the GEMM streams the
+        e4m3 weight (fp32-wire and registered-output variants included)."""
         fp32_wire = self.allreduce_dtype == "fp32"
         fp8 = self.gemm_dtype == "fp8"
+        w8 = decode and self.decode_weight_dtype == "fp8"
         if self.kernels == "torch":
-            y = (ops.fp8_linear(x, self.weight, kernels="torch") if fp8
+            y = (ops.w8_linear(x, self.weight, kernels="torch") if w8
+                 else ops.fp8_linear(x, self.weight, kernels="torch") if fp8
                  else x @ self.weight.t())
             if fp32_wire:
                 y = y.float()
@@ -216,10 +241,14 @@ class RowParallelLinear(nn.Module):
         if reg is not None:
             buf, rid = reg
             y = buf.view(*x.shape[:-1], self.out_features)
-            if fp8:
+            if w8:
+                ops.w8_linear(x, self.weight, out_dtype=odt, out=y)
+            elif fp8:
                 ops.fp8_linear(x, self.weight, out_dtype=odt, out=y)
             else:
                 ops.linear(x, self.weight, out_dtype=odt, out=y)
+        elif w8:
+            y = ops.w8_linear(x, self.weight, out_dtype=odt)
         elif fp8:
             y = ops.fp8_linear(x, self.weight, out_dtype=odt)
         else:

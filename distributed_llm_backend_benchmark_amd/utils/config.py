@@ -25,6 +25,12 @@ Additions (all optional, defaults keep reference behaviour):
 * ``execution.gemm_dtype``: ``bf16`` (default) | ``fp8`` — the TP linears quantise activations
   per token and weights per output row to e4m3 and run the FP8 GEMM (``ops.fp8``); needs the
   hidden and FFN widths of one rank's shard to be multiples of 128.
+* ``execution.decode_weight_dtype``: ``bf16`` (default) | ``fp8`` — the one-token decode steps
+  (``decode_tokens``) stream every linear's weight as e4m3 with one scale per output row through
+  the weight-only FP8 skinny GEMM (bf16 activations; ``run_tp --decode-weights``); needs the
+  hidden size and one rank's hidden and FFN widths to be multiples of 64, a batch of at most 16,
+  and keeps both copies of the weights resident (+ 50 % weight memory). Not with ``gemm_dtype:
+  fp8``.
 """
 
 from __future__ import annotations
@@ -56,6 +62,7 @@ DEFAULT_CONFIG: Dict[str, Any] = {
         "overlap_chunks": 1,
         "gemm_dtype": "bf16",
         "decode_tokens": 0,
+        "decode_weight_dtype": "bf16",
     },
     "system": {"omp_num_threads": 14, "mkl_num_threads": 14},
 }
@@ -126,6 +133,11 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
         raise ConfigError(f"execution.gemm_dtype must be bf16|fp8, got {ex['gemm_dtype']!r}")
     if ex["gemm_dtype"] == "fp8":
         check_fp8_shapes(cfg, ws if isinstance(ws, int) else 1)
+    if ex["decode_weight_dtype"] not in ("bf16", "fp8"):
+        raise ConfigError("execution.decode_weight_dtype must be bf16|fp8, got "
+                          f"{ex['decode_weight_dtype']!r}")
+    if ex["decode_weight_dtype"] == "fp8":
+        check_w8_shapes(cfg, ws if isinstance(ws, int) else 1)
     return cfg
 
 
@@ -140,6 +152,24 @@ def check_fp8_shapes(config: Dict[str, Any], world: int) -> None:
         if width % world or (width // world) % 128:
             raise ConfigError(f"execution.gemm_dtype=fp8 needs model.{key} / {world} ranks to be "
                               f"a multiple of 128, got {width} / {world}")
+
+
+def check_w8_shapes(config: Dict[str, Any], world: int) -> None:
+    """The weight-only FP8 skinny GEMM of the decode steps reduces over units of 64 and writes
+    tiles of 16 output columns: the hidden size (the column-parallel reductions) and the per-rank
+    shard widths ``hidden_size / world`` and ``ffn_intermediate / world`` (the row-parallel
+    reductions) must be multiples of 64. Every per-rank output width (``3 hidden_size / world``,
+    ``ffn_intermediate / world``, ``hidden_size``) is then a multiple of 16 as well. ``world`` as
+    in :func:`check_fp8_shapes`."""
+    m = config["model"]
+    hidden, ffn = int(m["hidden_size"]), int(m["ffn_intermediate"])
+    if hidden % 64:
+        raise ConfigError("execution.decode_weight_dtype=fp8 needs model.hidden_size to be a "
+                          f"multiple of 64, got {hidden}")
+    for key, width in (("hidden_size", hidden), ("ffn_intermediate", ffn)):
+        if width % world or (width // world) % 64:
+            raise ConfigError(f"execution.decode_weight_dtype=fp8 needs model.{key} / {world} "
+                              f"ranks to be a multiple of 64, got {width} / {world}")
 
 
 def load_config(config_path: str) -> Dict[str, Any]:

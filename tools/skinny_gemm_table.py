@@ -3,15 +3,22 @@
 of the ``ops.linear`` dispatch whose contract holds (``mfma``, ``mfma_sk``, ``mfma_split``,
 ``blas`` = hipBLASLt) on the decode step's shapes, and against a bandwidth floor.
 
-Rows: the eight M = 8 shapes of the 7B decode step (four at world 1, four on rank 0's shard of
-an 8-way run) plus the shard-8 QKV shape at M = 1 and M = 16.
+``mfma_skinny_w8`` is the weight-only FP8 form of the skinny kernel (``csrc/gemm_skinny_w8.hip``,
+``ops.fp8.linear_w8``): not a dispatch candidate (it changes numerics), timed beside the others on
+the e4m3 copy of the same weights, with its own floor ``copy_w8`` — the copy of the e4m3 bytes —
+and its ratio to ``mfma_skinny`` (the bytes say 0.5).
+
+Rows: the sixteen M = 8 shapes of the 7B decode step (four each at world 1 and on rank 0's shard
+of a 2-, 4- and 8-way run) plus the shard-8 QKV shape at M = 1 and M = 16. ``--candidates``
+restricts what is timed (``mfma_skinny`` and the copies always are).
 
 All candidates of a row are timed in ONE process, each as a HIP graph of ``--inner`` (10)
 back-to-back calls, median of ``--rounds`` (9) alternating rounds, twice:
 
 * **cold**: the calls rotate over enough distinct copies of W to exceed the 256 MiB last-level
   cache (``--rotate-mb``; as many 10-call graphs as it takes to walk all copies, replayed in
-  turn), as the 32 layers of a decode step do;
+  turn), as the 32 layers of a decode step do; the e4m3 weights are half the size, so there are
+  twice as many of them;
 * **warm**: one W, as the autotuner times its candidates.
 
 The floor is ``dst.copy_(src)`` of the same W bytes. The copy moves the bytes twice (read +
@@ -40,12 +47,19 @@ sys.path.insert(0, REPO)
 # (label, M, N, K): config/7b_config.yaml, hidden 4096, ffn 16384, batch 8
 DEFAULT_ROWS = [("w1 qkv", 8, 12288, 4096), ("w1 out", 8, 4096, 4096),
                 ("w1 up", 8, 16384, 4096), ("w1 down", 8, 4096, 16384),
+                ("s2 qkv", 8, 6144, 4096), ("s2 out", 8, 4096, 2048),
+                ("s2 up", 8, 8192, 4096), ("s2 down", 8, 4096, 8192),
+                ("s4 qkv", 8, 3072, 4096), ("s4 out", 8, 4096, 1024),
+                ("s4 up", 8, 4096, 4096), ("s4 down", 8, 4096, 4096),
                 ("s8 qkv", 8, 1536, 4096), ("s8 out", 8, 4096, 512),
                 ("s8 up", 8, 2048, 4096), ("s8 down", 8, 4096, 2048),
                 ("s8 qkv M=1", 1, 1536, 4096), ("s8 qkv M=16", 16, 1536, 4096)]
 
 
-def candidates(gemm, x, w, out):
+W8 = "mfma_skinny_w8"
+
+
+def candidates(gemm, x, w, out, only=None):
     M, K = x.shape
     N = w.shape[0]
     names = ["mfma_skinny", "mfma"]
@@ -55,6 +69,8 @@ def candidates(gemm, x, w, out):
         names.append("mfma_split")
     names.append("blas")
     assert gemm.skinny_ok(x, w, out), "row outside the skinny contract"
+    if only is not None:
+        names = [n for n in names if n == "mfma_skinny" or n in only]
     return names
 
 
@@ -94,7 +110,7 @@ def _time(torch, graph_sets, inner, rounds):
 def bench_row(label, M, N, K, args):
     import torch
 
-    from distributed_llm_backend_benchmark_amd.ops import gemm
+    from distributed_llm_backend_benchmark_amd.ops import fp8, gemm
 
     dev = torch.device("cuda", 0)
     w_bytes = N * K * 2
@@ -105,7 +121,8 @@ def bench_row(label, M, N, K, args):
     x = (torch.rand(M, K, generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
     sink = torch.empty_like(ws[0])
-    names = candidates(gemm, x, ws[0], out)
+    names = candidates(gemm, x, ws[0], out, args.candidates)
+    with_w8 = args.candidates is None or W8 in args.candidates
     before = gemm.SKINNY_LAUNCHES["count"]
     ref = x.float() @ ws[0].float().t()
     errs = {}
@@ -113,6 +130,16 @@ def bench_row(label, M, N, K, args):
         gemm._IMPLS[n](x, ws[0], None, None, None, out, None)
         errs[n] = float((out.float() - ref).norm() / ref.norm())
     assert gemm.SKINNY_LAUNCHES["count"] == before + 1
+    nbuf8 = 0
+    if with_w8:
+        # e4m3 copies of the same weights, and as many again to rotate over the same bytes
+        nbuf8 = max(1, -(-args.rotate_mb * (1 << 20) // (w_bytes // 2)))
+        q8 = [fp8.quantize_rows(ws[i % nbuf]) for i in range(nbuf8)]
+        sink8 = torch.empty_like(q8[0][0])
+        before = fp8.W8_LAUNCHES["count"]
+        fp8.linear_w8(x, q8[0][0], q8[0][1], out=out)
+        assert fp8.W8_LAUNCHES["count"] == before + 1
+        errs[W8] = float((out.float() - ref).norm() / ref.norm())
 
     def call(n):
         f = gemm._IMPLS[n]
@@ -120,11 +147,18 @@ def bench_row(label, M, N, K, args):
 
     fns = {n: call(n) for n in names}
     fns["copy"] = lambda i: sink.copy_(ws[i % nbuf])
-    cold = _time(torch, {n: _graphs(torch, f, nbuf, args.inner) for n, f in fns.items()},
+    walk = {n: nbuf for n in fns}                        # distinct weights each candidate walks
+    if with_w8:
+        fns[W8] = lambda i: fp8.linear_w8(x, *q8[i % nbuf8], out=out)
+        fns["copy_w8"] = lambda i: sink8.copy_(q8[i % nbuf8][0])
+        walk[W8] = walk["copy_w8"] = nbuf8
+    cold = _time(torch, {n: _graphs(torch, f, walk[n], args.inner) for n, f in fns.items()},
                  args.inner, args.rounds)
     warm = _time(torch, {n: _graphs(torch, (lambda i, f=f: f(0)), 1, args.inner)
                          for n, f in fns.items()}, args.inner, args.rounds)
     del ws, sink
+    if with_w8:
+        del q8, sink8
     plan = gemm.skinny_plan(M, N, K, gemm._num_cus(dev))
     row = {"row": label, "M": M, "N": N, "K": K, "w_bytes": w_bytes, "rotated_weights": nbuf,
            "inner": args.inner, "rounds": args.rounds,
@@ -133,38 +167,63 @@ def bench_row(label, M, N, K, args):
            "rel_frobenius_err": {n: round(v, 6) for n, v in errs.items()}}
     for tag, (med, mn) in (("cold", cold), ("warm", warm)):
         others = [n for n in names if n != "mfma_skinny"]
-        best = min(others, key=lambda n: med[n])
+        best = min(others, key=lambda n: med[n]) if others else None    # --candidates left none
         row[tag] = {"us": {n: round(t, 2) for n, t in med.items()},
                     "us_min": {n: round(t, 2) for n, t in mn.items()},
                     "best_other": best,
-                    "skinny_over_best_other": round(med["mfma_skinny"] / med[best], 3),
+                    "skinny_over_best_other": (round(med["mfma_skinny"] / med[best], 3)
+                                               if best else None),
                     "fastest": min(names, key=lambda n: med[n]),
                     "skinny_GBps": round(w_bytes / med["mfma_skinny"] / 1e3, 1),
                     "copy_GBps_2x_bytes": round(2 * w_bytes / med["copy"] / 1e3, 1),
                     "share_of_copy": round(med["copy"] / (2 * med["mfma_skinny"]), 3)}
+        if with_w8:
+            # the W8 kernel: its e4m3 read rate, the copy of those bytes (moved twice), and its
+            # time over the bf16 skinny kernel's in the same alternating rounds
+            row[tag].update(
+                w8_over_skinny=round(med[W8] / med["mfma_skinny"], 3),
+                w8_GBps=round(w_bytes / 2 / med[W8] / 1e3, 1),
+                copy_w8_GBps_2x_bytes=round(w_bytes / med["copy_w8"] / 1e3, 1),
+                w8_share_of_copy=round(med["copy_w8"] / (2 * med[W8]), 3))
+    if with_w8:
+        p8 = fp8.w8_skinny_plan(M, N, K, gemm._num_cus(dev))
+        row["w8_bytes"], row["rotated_weights_w8"] = w_bytes // 2, nbuf8
+        row["plan_w8"] = {"grid": p8[0], "k_split_in_workgroup": p8[1]}
     return row
 
 
+def _ratio(t) -> str:
+    if t["best_other"] is None:
+        return "n/a"
+    return f"{t['skinny_over_best_other']:.2f} ({t['best_other']})"
+
+
 def summary(rows) -> str:
-    cols = ["mfma_skinny", "mfma", "mfma_sk", "mfma_split", "blas", "copy"]
+    cols = ["mfma_skinny", W8, "mfma", "mfma_sk", "mfma_split", "blas", "copy", "copy_w8"]
     lines = ["# Skinny-M GEMM table (`tools/skinny_gemm_table.py`)", "",
              "µs per call (HIP graph of 10 calls, median of 9 alternating rounds). cold = calls "
              "rotate over > 256 MiB of distinct weights; warm = one weight. copy = "
              "`dst.copy_(src)` of the W bytes (moves them twice; GB/s over 2x the bytes). "
-             "plan = workgroups x waves per workgroup (K-split inside the workgroup).", ""]
+             "plan = workgroups x waves per workgroup (K-split inside the workgroup). "
+             f"{W8} = the weight-only FP8 skinny kernel on the e4m3 copy of W (half the bytes; "
+             "copy_w8 = the copy of those); W8 / skinny = its time over mfma_skinny's; W8 share = "
+             "its e4m3 read rate over copy_w8's rate.", ""]
     for tag in ("cold", "warm"):
         lines += [f"## {tag}", "",
                   "| row | M, N, K | W | plan | " + " | ".join(cols) +
-                  " | skinny / best other | skinny GB/s | copy GB/s | fastest |",
-                  "|" + "---|" * (len(cols) + 8)]
+                  " | skinny / best other | skinny GB/s | copy GB/s | fastest | W8 / skinny | "
+                  "W8 GB/s | W8 share |",
+                  "|" + "---|" * (len(cols) + 11)]
         for r in rows:
             t = r[tag]
             us = " | ".join(f"{t['us'][c]:.1f}" if c in t["us"] else "n/a" for c in cols)
             lines.append(
                 f"| {r['row']} | {r['M']}, {r['N']}, {r['K']} | {r['w_bytes'] / 2**20:.0f} MiB | "
                 f"{r['plan']['grid']} x {r['plan']['k_split_in_workgroup']} | {us} | "
-                f"{t['skinny_over_best_other']:.2f} ({t['best_other']}) | {t['skinny_GBps']:.0f} | "
-                f"{t['copy_GBps_2x_bytes']:.0f} | {t['fastest']} |")
+                f"{_ratio(t)} | {t['skinny_GBps']:.0f} | "
+                f"{t['copy_GBps_2x_bytes']:.0f} | {t['fastest']} | " +
+                (f"{t['w8_over_skinny']:.2f} | {t['w8_GBps']:.0f} | {t['w8_share_of_copy']:.2f} |"
+                 if "w8_over_skinny" in t else "n/a | n/a | n/a |"))
         lines.append("")
     diff = [r["row"] for r in rows if r["cold"]["fastest"] != r["warm"]["fastest"]]
     lines.append("Rows whose cold and warm rankings name a different fastest candidate: "
@@ -226,6 +285,8 @@ def main(argv=None) -> int:
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--rotate-mb", type=int, default=320)
+    ap.add_argument("--candidates", nargs="*", default=None, metavar="NAME",
+                    help=f"time only these beside mfma_skinny and the copies (e.g. {W8})")
     ap.add_argument("--out-dir", default=os.path.join(REPO, "profiles", "skinny_gemm"))
     ap.add_argument("--pmc-loop", type=int, default=0, metavar="N")
     ap.add_argument("--pmc-csv", nargs="+", default=None, metavar="FILE")
@@ -252,8 +313,10 @@ def main(argv=None) -> int:
                 print(f"{label} [{M},{N},{K}] {tag}: " +
                       "  ".join(f"{n} {v:.1f}" for n, v in t["us"].items()) +
                       f" us | skinny {t['skinny_GBps']:.0f} GB/s, copy "
-                      f"{t['copy_GBps_2x_bytes']:.0f} GB/s, skinny/best other "
-                      f"{t['skinny_over_best_other']:.2f} ({t['best_other']})", flush=True)
+                      f"{t['copy_GBps_2x_bytes']:.0f} GB/s, skinny/best other {_ratio(t)}" +
+                      (f", W8/skinny {t['w8_over_skinny']:.2f}, W8 share of its copy "
+                       f"{t['w8_share_of_copy']:.2f}" if "w8_over_skinny" in t else ""),
+                      flush=True)
     with open(os.path.join(args.out_dir, "SUMMARY.md"), "w") as f:
         f.write(summary(done))
     return 0
