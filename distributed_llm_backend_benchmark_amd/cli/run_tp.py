@@ -22,7 +22,10 @@ step replayed N times where the forward is capturable; ``--eager`` issues them f
 The record gets a ``decode`` section (``ms_per_token``, ``achieved_GBps``, ...) and the file name
 the suffix ``_decode<N>``. ``--decode-weights fp8`` streams the e4m3 copy of every linear's weight
 in those steps (weight-only FP8, bf16 activations): suffix ``_decode<N>_w8``, and the ``decode``
-section counts the streamed bytes.
+section counts the streamed bytes. ``--kv-cache fp8`` keeps the KV cache of those steps as e4m3
+codes with one fp32 scale per cached row (``ops.decode``): suffix ``_kv8`` (after ``_w8``), the
+``decode`` section carries ``kv_dtype`` and counts codes + scales in its cache and K / V bytes. It
+composes with ``--decode-weights fp8`` and needs decode tokens and a real attention (not ``slice``).
 """
 
 from __future__ import annotations
@@ -98,6 +101,11 @@ def parse_args(argv=None):
                          "(execution.decode_weight_dtype): fp8 = e4m3 with per-output-row scales "
                          "on the weight-only FP8 skinny GEMM, bf16 activations, batch <= 16; "
                          "output file gets the suffix _w8")
+    ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default=None,
+                    help="with --decode: storage of the KV cache (execution.kv_cache_dtype): fp8 = "
+                         "e4m3 codes with one fp32 scale per cached row, head_dim + 4 bytes per "
+                         "row instead of 2 head_dim; not with attention slice (no cache); output "
+                         "file gets the suffix _kv8")
     ap.add_argument("--max-len", type=int, default=None, metavar="L",
                     help="with --decode: positions of the KV cache (default sequence_length + N)")
     ap.add_argument("--check-dense", action="store_true",
@@ -165,6 +173,17 @@ def main(argv=None) -> int:
     if args.decode_weights:
         ex["decode_weight_dtype"] = args.decode_weights
     w8 = ex.get("decode_weight_dtype", "bf16") == "fp8"
+    if args.kv_cache:
+        ex["kv_cache_dtype"] = args.kv_cache
+    kv8 = ex.get("kv_cache_dtype", "bf16") == "fp8"
+    if kv8 and (not n_dec or ex.get("attention", "slice") == "slice"):
+        # refused before any process group exists: nothing to quantise, never a silent bf16 run
+        if os.environ.get("RANK", "0") == "0":
+            print("ERROR: --kv-cache fp8 (execution.kv_cache_dtype) needs " +
+                  ("decode tokens (--decode N): only the decode steps keep a KV cache"
+                   if not n_dec else
+                   "attention sdpa or flash: attention slice keeps no K / V to quantise"))
+        return 1
     prompt = int(config["input"]["sequence_length"])
     max_len = int(args.max_len) if args.max_len else prompt + n_dec
     if n_dec and max_len < prompt + n_dec:
@@ -468,13 +487,14 @@ def main(argv=None) -> int:
         if extra["gemm_dtype"] != "bf16":      # never overwrites the bf16 record
             suffix += f"_{extra['gemm_dtype']}"
         if dec is not None:                    # never overwrites the prefill record
-            suffix += f"_decode{n_dec}" + ("_w8" if w8 else "")
+            suffix += f"_decode{n_dec}" + ("_w8" if w8 else "") + ("_kv8" if kv8 else "")
             d = results["decode"]
             print(f"  decode: {d['ms_per_token_mean']:.4f} ms/token ({d['timing_mode']}, "
                   f"attention {d['attention_path']}), {d['decode_tokens_per_s']:.0f} tokens/s, "
                   f"{d['achieved_GBps']:.0f} GB/s of weights + KV" +
                   (f" ({d['weight_dtype']} weights, {d['w8_launches_per_step']} W8 launches "
-                   "per step)" if w8 else ""))
+                   "per step)" if w8 else "") +
+                  (f" ({d['kv_dtype']} KV cache)" if kv8 else ""))
         out = os.path.join(config["experiment"]["output_dir"],
                            f"{args.backend}_{config['experiment']['name']}{suffix}.json")
         save_results(results, out, rank)
@@ -513,7 +533,9 @@ class _DecodeRunner:
             self.attention_path = "hip"
         else:
             self.attention_path = "torch"
-        self.kv_per_key = cache.num_layers * cache.batch * heads * hd * 2 * 2   # K + V, bf16
+        # bytes of one cached position: K + V rows of hd bf16, or of hd e4m3 codes + an fp32 scale
+        row_bytes = hd + 4 if cache.kv_dtype == "fp8" else 2 * hd
+        self.kv_per_key = cache.num_layers * cache.batch * heads * row_bytes * 2
         self.x = torch.empty(batch.shape[0], 1, batch.shape[2], dtype=batch.dtype,
                              device=batch.device)
         self.dev_ms, self.host_ms = [], []
@@ -626,6 +648,7 @@ class _DecodeRunner:
             # the GEMM shapes of a decode step (M = batch rows) and what the autotuner runs there
             "gemm_kernel_mix": {"shapes_by_choice": by_choice, "tuned": tuned},
             "weight_dtype": self.model.decode_weight_dtype,
+            "kv_dtype": self.cache.kv_dtype,
         }
         if w8:
             # the e4m3 bytes and row scales of every linear (+ the LayerNorm parameters): what a

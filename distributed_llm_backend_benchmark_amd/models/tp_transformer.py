@@ -22,6 +22,9 @@ per-token activation scales, per-output-row weight scales); the default stays bf
 ``decode_weight_dtype="fp8"`` (opt-in) streams the e4m3 copy of every linear's weight in those
 decode steps (``ops.w8_linear``, bf16 activations); prefill and cache-less forwards keep the bf16
 weights. Both copies are resident: + 50 % weight memory.
+``kv_cache_dtype="fp8"`` (opt-in) makes ``new_kv_cache`` hold e4m3 codes with one fp32 scale per
+cached row (``ops.decode``): the appends quantise, a decode step attends to the quantised rows, the
+prefill attention itself stays on the bf16 ``qkv``.
 """
 
 from __future__ import annotations
@@ -131,17 +134,20 @@ class TransformerBlock(nn.Module):
         from ..ops import decode as dec
 
         k, v = cache.k[layer], cache.v[layer]
+        # the row scales of an FP8 cache (None for bf16): handed through as they are
+        ks, vs = cache.k_scale[layer], cache.v_scale[layer]
         hip = self.attention == "flash" and self.kernels != "torch"
         if qkv.shape[1] == 1:
             if hip:
                 return ops.decode_attention(qkv, heads, k, v, cache.length,
                                             len_bound=cache.len_bound,
-                                            workspace=cache.workspace, pos=cache.pos)
-            return dec.torch_decode_attention(qkv, heads, k, v, cache.pos)
+                                            workspace=cache.workspace, pos=cache.pos,
+                                            k_scale=ks, v_scale=vs)
+            return dec.torch_decode_attention(qkv, heads, k, v, cache.pos, ks, vs)
         if hip:
-            ops.kv_append(qkv, heads, k, v, cache.length, pos=cache.pos)
+            ops.kv_append(qkv, heads, k, v, cache.length, pos=cache.pos, k_scale=ks, v_scale=vs)
             return ops.causal_attention(qkv, heads)
-        dec.torch_kv_append(qkv, heads, k, v, cache.pos)
+        dec.torch_kv_append(qkv, heads, k, v, cache.pos, ks, vs)
         return self._attn(qkv)
 
     def forward(self, y1: torch.Tensor, h: torch.Tensor):
@@ -177,8 +183,11 @@ class LLM(nn.Module):
                  comm: Comm, seed: int = 0, init_std: float = 1.0, allreduce: str = "rccl",
                  allreduce_dtype: str = "bf16", attention: str = "slice", kernels: str = "hip",
                  overlap_chunks: int = 1, gemm_dtype: str = "bf16",
-                 decode_weight_dtype: str = "bf16"):
+                 decode_weight_dtype: str = "bf16", kv_cache_dtype: str = "bf16"):
         super().__init__()
+        if kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache_dtype must be bf16|fp8, got {kv_cache_dtype!r}")
+        self.kv_cache_dtype = kv_cache_dtype
         self.gemm_dtype = gemm_dtype
         self.decode_weight_dtype = _check_decode_weight_dtype(decode_weight_dtype, gemm_dtype)
         self.attention = attention
@@ -222,7 +231,8 @@ class LLM(nn.Module):
         positions. ``attention="slice"`` (the stateless stub) gets one with no K / V storage:
         decode still runs, and measures the GEMMs and the ``[B, 1, H]`` all-reduces alone.
         With ``decode_weight_dtype="fp8"`` on the HIP path the batch is the M of the W8 skinny
-        GEMM: more than 16 rows raise here, not in the middle of a step."""
+        GEMM: more than 16 rows raise here, not in the middle of a step. ``kv_cache_dtype``
+        picks the cache's storage (``"fp8"``: e4m3 codes + one fp32 scale per row)."""
         if (self.decode_weight_dtype == "fp8" and batch > 16 and self.kernels != "torch"
                 and self.comm.device.type == "cuda" and not ops._lib.force_torch()):
             raise ValueError(f"decode_weight_dtype='fp8': batch {batch} is larger than the 16 "
@@ -230,7 +240,7 @@ class LLM(nn.Module):
         heads = self.num_heads // self.world_size
         layers = 0 if self.attention == "slice" else self.num_layers
         return ops.KVCache(layers, batch, heads, self.hidden_size // self.num_heads, max_len,
-                           self.comm.device)
+                           self.comm.device, kv_dtype=self.kv_cache_dtype)
 
     def _micro_batch(self, x: torch.Tensor, slot: int = 0, stream=None, cache=None):
         """One micro-batch's forward as a generator over its all-reduces (see
@@ -410,4 +420,5 @@ def create_model_from_config(config: Dict, comm: Comm) -> LLM:
                attention=ex.get("attention", "slice"), kernels=ex.get("kernels", "hip"),
                overlap_chunks=int(ex.get("overlap_chunks", 1)),
                gemm_dtype=ex.get("gemm_dtype", "bf16"),
-               decode_weight_dtype=ex.get("decode_weight_dtype", "bf16"))
+               decode_weight_dtype=ex.get("decode_weight_dtype", "bf16"),
+               kv_cache_dtype=ex.get("kv_cache_dtype", "bf16"))

@@ -8,7 +8,8 @@
 * :mod:`.norm_act` — fused residual+LayerNorm and bias+GELU (fwd + bwd, autograd).
 * :mod:`.optim` — flat fused AdamW.
 * :mod:`.xent` — fused softmax cross-entropy on bf16 logits; LM-head-fused linear + loss.
-* :mod:`.decode` — KV cache, append, and single-query (decode) attention split over the keys.
+* :mod:`.decode` — KV cache (bf16, or opt-in e4m3 codes with one fp32 scale per row), append, and
+  single-query (decode) attention split over the keys.
 * :mod:`.embedding` — token + position embedding, backward accumulating in place (sinks).
 * :mod:`._lib` — loader; ``available()``, ``loaded_path()``.
 """
@@ -22,10 +23,10 @@ from .norm_act import layernorm, bias_gelu
 from .optim import FlatAdamW
 from .xent import cross_entropy, linear_cross_entropy
 from .attention import causal_attention
-from .decode import KVCache, kv_append, decode_attention, CHUNK
+from .decode import KVCache, kv_append, decode_attention, CHUNK, CHUNK_FP8
 from .embedding import embedding
 
-__all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
+__all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "CHUNK_FP8", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
            "ChunkTable", "ScaleTable", "flatten_into", "linear", "layernorm", "bias_gelu",
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
            "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES"]

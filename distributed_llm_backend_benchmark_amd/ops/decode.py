@@ -21,6 +21,29 @@ CPU tensors, ``DLBB_KERNELS=torch`` and other head dims use torch (:func:`torch_
 :func:`torch_decode_attention`): an index copy into the cache and
 ``F.scaled_dot_product_attention`` on ``cache[:, :, :pos + 1]``. That path slices by the HOST
 position, so it is not replayable across positions in a captured graph.
+
+FP8 cache (opt-in, ``KVCache(kv_dtype="fp8")``; ``csrc/attn_decode_kv8.hip``). The contract:
+
+* ``k_cache`` / ``v_cache`` are ``[B, H_local, L_max, D]`` ``torch.float8_e4m3fn``, contiguous;
+  ``k_scale`` / ``v_scale`` are ``[B, H_local, L_max]`` fp32, contiguous: one scale per cached
+  row of ``D`` values, ``row ~= float(code) * scale``.
+* A row is quantised exactly as :mod:`.fp8` quantises one (``fp8._quantize_torch`` is the
+  reference, compared bit for bit): ``amax == 0`` gives scale 1 and bytes 0; otherwise ``inv =
+  448 / amax``, ``scale = amax / 448`` (IEEE fp32 divisions) and ``code = e4m3fn_rne(float(x) *
+  inv)``.
+* A row stores ``D + 4`` bytes against ``2 D``: 0.516 of the bf16 cache at D = 128, 0.531 at 64.
+* A decode step stores the new token QUANTISED and attends to it in its quantised form: the
+  step's result is attention over the cache contents after the append, exactly, and a replayed
+  graph gives the same bits as eager. The prefill is unchanged: it attends over the bf16 ``qkv``
+  it was given, only its :func:`kv_append` quantises.
+* ``length``, ``len_bound``, the fp32 ``(m, l, o[D])`` workspace and the combine step keep their
+  meaning; the split runs in chunks of :data:`CHUNK_FP8` keys.
+
+:func:`kv_append` / :func:`decode_attention` take the scales as ``k_scale`` / ``v_scale``
+(``None`` = the bf16 cache). The dispatch rule is the same: the HIP kernels on a GPU tensor with
+head dim 64 / 128 and contiguous bf16 ``qkv``; the torch forms otherwise (the append quantises
+with ``fp8._quantize_torch``, the decode dequantises ``cache[:, :, :pos + 1]`` to fp32 and runs
+SDPA).
 """
 
 from __future__ import annotations
@@ -34,10 +57,17 @@ import torch.nn.functional as F
 from . import _lib
 from ._lib import check, use_hip
 from .attention import HEAD_DIMS, _views
+from .fp8 import E4M3, _quantize_torch
 
 # keys per workgroup of the split kernel (csrc/attn_decode.hip takes it per launch; the
 # alternatives measured are in docs/PERFORMANCE.md)
 CHUNK = 256
+# keys per workgroup of the FP8-cache split kernel (csrc/attn_decode_kv8.hip), a constant of its
+# own: a 256-key chunk holds half the bytes there. 256 / 512 / 1024 measured (docs/PERFORMANCE.md):
+# 512 is 10-15 % faster on the rows of >= 128 MiB of bf16 K + V and 6-32 % slower on the smaller
+# head-dim-128 ones, 1024 is 3-17 % faster from 256 MiB and up to 67 % slower below
+CHUNK_FP8 = 256
+KV_DTYPES = ("bf16", "fp8")
 # append + attend in one launch (the chunk owning position `length` takes the token's K / V from
 # qkv and stores them) instead of a kv_append launch before the attention
 FUSED_APPEND = True
@@ -52,12 +82,20 @@ def workspace_numel(batch: int, n_head: int, head_dim: int, max_len: int,
 class KVCache:
     """K / V of every layer of one rank, the shared device ``length``, and the split kernel's
     workspace. ``num_layers = 0`` holds no K / V (the stateless ``attention="slice"`` stub):
-    only the position bookkeeping."""
+    only the position bookkeeping. ``kv_dtype="fp8"``: ``k`` / ``v`` hold e4m3 codes and
+    ``k_scale`` / ``v_scale`` one fp32 scale per cached row (module docstring); with ``"bf16"``
+    the two scale lists hold ``None`` per layer."""
 
     def __init__(self, num_layers: int, batch: int, n_head_local: int, head_dim: int,
-                 max_len: int, device, dtype=torch.bfloat16):
+                 max_len: int, device, dtype=torch.bfloat16, kv_dtype: str = "bf16"):
         if max_len < 1 or batch < 1:
             raise ValueError(f"KVCache needs batch >= 1 and max_len >= 1, got {batch}, {max_len}")
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"KVCache kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
+        fp8 = kv_dtype == "fp8"
+        if fp8:
+            dtype = E4M3
         self.num_layers, self.batch = int(num_layers), int(batch)
         self.n_head, self.head_dim, self.max_len = int(n_head_local), int(head_dim), int(max_len)
         self.device = torch.device(device)
@@ -66,13 +104,19 @@ class KVCache:
                                       for _ in range(self.num_layers)]
         self.v: List[torch.Tensor] = [torch.zeros(shape, dtype=dtype, device=self.device)
                                       for _ in range(self.num_layers)]
+        self.k_scale: List[Optional[torch.Tensor]] = [
+            torch.ones(shape[:3], dtype=torch.float32, device=self.device) if fp8 else None
+            for _ in range(self.num_layers)]
+        self.v_scale: List[Optional[torch.Tensor]] = [
+            torch.ones(shape[:3], dtype=torch.float32, device=self.device) if fp8 else None
+            for _ in range(self.num_layers)]
         self.length = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.pos = 0                    # host mirror of `length`: bounds checks only
         # host upper bound of length + 1 for the split grid (None = max_len); a runner that
         # replays one captured step sets the final position here before the capture
         self.len_bound: Optional[int] = None
         self.workspace = (torch.empty(workspace_numel(self.batch, self.n_head, self.head_dim,
-                                                      self.max_len),
+                                                      self.max_len, CHUNK_FP8 if fp8 else CHUNK),
                                       dtype=torch.float32, device=self.device)
                           if self.num_layers else None)
 
@@ -96,17 +140,25 @@ class KVCache:
 
     @property
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.k + self.v)
+        """Bytes of K and V over every layer (codes and scales for the FP8 cache)."""
+        return sum(t.numel() * t.element_size()
+                   for t in self.k + self.v + self.k_scale + self.v_scale if t is not None)
 
 
 def hip_supported(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
-                  v_cache: torch.Tensor) -> bool:
+                  v_cache: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
+                  v_scale: Optional[torch.Tensor] = None) -> bool:
     if qkv.dim() != 3 or qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
         return False
     C = qkv.shape[2] // 3
     if qkv.shape[2] % 3 or C % n_head or C // n_head not in HEAD_DIMS:
         return False
     shape = (qkv.shape[0], n_head, k_cache.shape[2] if k_cache.dim() == 4 else -1, C // n_head)
+    if k_scale is not None or v_scale is not None:
+        return (all(t.dtype == E4M3 and t.is_contiguous() and tuple(t.shape) == shape
+                    for t in (k_cache, v_cache))
+                and all(t is not None and t.dtype == torch.float32 and t.is_contiguous()
+                        and tuple(t.shape) == shape[:3] for t in (k_scale, v_scale)))
     return all(t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == shape
                for t in (k_cache, v_cache))
 
@@ -115,33 +167,81 @@ def _host_pos(length: torch.Tensor, pos: Optional[int]) -> int:
     return int(length.item()) if pos is None else int(pos)
 
 
-def torch_kv_append(qkv, n_head: int, k_cache, v_cache, pos: int) -> None:
+def _check_fp8_cache(k_cache, v_cache, k_scale, v_scale) -> bool:
+    """True for the FP8 cache (both scales given), False for bf16 (neither); raises on a mix."""
+    if k_scale is None and v_scale is None:
+        if k_cache.dtype == E4M3 or v_cache.dtype == E4M3:
+            raise ValueError("an e4m3 KV cache needs its k_scale / v_scale")
+        return False
+    if k_scale is None or v_scale is None:
+        raise ValueError("k_scale and v_scale go together")
+    if k_cache.dtype != E4M3 or v_cache.dtype != E4M3:
+        raise ValueError(f"k_scale / v_scale go with an e4m3 KV cache, got {k_cache.dtype} / "
+                         f"{v_cache.dtype}")
+    if k_scale.dtype != torch.float32 or v_scale.dtype != torch.float32 \
+            or tuple(k_scale.shape) != tuple(k_cache.shape[:3]) \
+            or tuple(v_scale.shape) != tuple(v_cache.shape[:3]):
+        raise ValueError("k_scale / v_scale must be fp32 [B, H, L_max]")
+    return True
+
+
+def torch_kv_append(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
+                    v_scale=None) -> None:
     """Torch form of :func:`kv_append` at the host position ``pos``."""
     T = qkv.shape[1]
     _, k, v = _views(qkv, n_head)
-    k_cache[:, :, pos:pos + T] = k
-    v_cache[:, :, pos:pos + T] = v
+    if k_scale is None:
+        k_cache[:, :, pos:pos + T] = k
+        v_cache[:, :, pos:pos + T] = v
+        return
+    for rows, cache, scale in ((k, k_cache, k_scale), (v, v_cache, v_scale)):
+        code, s = _quantize_torch(rows)
+        cache.view(torch.uint8)[:, :, pos:pos + T] = code.view(torch.uint8)
+        scale[:, :, pos:pos + T] = s
 
 
-def torch_decode_attention(qkv, n_head: int, k_cache, v_cache, pos: int) -> torch.Tensor:
+def dequantize(cache: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 rows of an FP8 cache (or a slice of one): ``float(code) * scale``."""
+    return cache.float() * scale[..., None]
+
+
+def torch_decode_attention(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
+                           v_scale=None) -> torch.Tensor:
     """Torch form of :func:`decode_attention` at the host position ``pos`` (not replayable
     across positions: the slice bound is a host value)."""
     B, _, C3 = qkv.shape
-    torch_kv_append(qkv, n_head, k_cache, v_cache, pos)
+    torch_kv_append(qkv, n_head, k_cache, v_cache, pos, k_scale, v_scale)
     q, _, _ = _views(qkv, n_head)
-    o = F.scaled_dot_product_attention(q, k_cache[:, :, :pos + 1], v_cache[:, :, :pos + 1])
+    if k_scale is None:
+        o = F.scaled_dot_product_attention(q, k_cache[:, :, :pos + 1], v_cache[:, :, :pos + 1])
+    else:
+        o = F.scaled_dot_product_attention(
+            q.float(), dequantize(k_cache[:, :, :pos + 1], k_scale[:, :, :pos + 1]),
+            dequantize(v_cache[:, :, :pos + 1], v_scale[:, :, :pos + 1])).to(qkv.dtype)
     return o.transpose(1, 2).reshape(B, 1, C3 // 3)
 
 
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
-              length: torch.Tensor, pos: Optional[int] = None) -> None:
+              length: torch.Tensor, pos: Optional[int] = None,
+              k_scale: Optional[torch.Tensor] = None,
+              v_scale: Optional[torch.Tensor] = None) -> None:
     """K / V rows of ``qkv [B, T, 3C]`` -> cache positions ``[length, length + T)``. ``pos``:
     the host's copy of ``length`` (raises before launch on overflow; None on the HIP path = no
-    host check, the kernel drops positions past the cache)."""
+    host check, the kernel drops positions past the cache). ``k_scale`` / ``v_scale``: the row
+    scales of an FP8 cache (module docstring), whose rows are quantised on the way in."""
     T, L_max = qkv.shape[1], k_cache.shape[2]
     if pos is not None and pos + T > L_max:
         raise ValueError(f"kv_append: position {pos} + {T} tokens > cache length {L_max}")
-    if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache):
+    fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+    if fp8 and use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale):
+        B, _, C3 = qkv.shape
+        check(_lib.lib().dlbb_kv_append_fp8(qkv.data_ptr(), C3, k_cache.data_ptr(),
+                                            v_cache.data_ptr(), k_scale.data_ptr(),
+                                            v_scale.data_ptr(), length.data_ptr(), B, T, n_head,
+                                            C3 // 3 // n_head, L_max, _lib.stream(qkv.device)),
+              "kv_append_fp8")
+        return
+    if not fp8 and use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache):
         B, _, C3 = qkv.shape
         check(_lib.lib().dlbb_kv_append(qkv.data_ptr(), C3, k_cache.data_ptr(),
                                         v_cache.data_ptr(), length.data_ptr(), B, T, n_head,
@@ -151,14 +251,15 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
     p = _host_pos(length, pos)
     if p + T > L_max:
         raise ValueError(f"kv_append: position {p} + {T} tokens > cache length {L_max}")
-    torch_kv_append(qkv, n_head, k_cache, v_cache, p)
+    torch_kv_append(qkv, n_head, k_cache, v_cache, p, k_scale, v_scale)
 
 
 def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, length: torch.Tensor,
                      len_bound: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
                      pos: Optional[int] = None, chunk: Optional[int] = None,
-                     fused: Optional[bool] = None) -> torch.Tensor:
+                     fused: Optional[bool] = None, k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One decode step of causal attention: ``qkv [B, 1, 3C]`` -> ``[B, 1, C]``; the token's
     K / V are stored at cache position ``length`` and the query attends over ``length + 1``
     keys. ``length`` is not advanced.
@@ -168,17 +269,20 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     every position below the bound. ``workspace``: the cache's fp32 partials buffer
     (:func:`workspace_numel`; allocated per call when None). ``pos``: the host's copy of
     ``length`` for the overflow check (and the torch path). ``chunk`` / ``fused``: A/B knobs of
-    ``tools/decode_bench.py`` (defaults :data:`CHUNK`, :data:`FUSED_APPEND`)."""
+    ``tools/decode_bench.py`` (defaults :data:`CHUNK`, :data:`FUSED_APPEND`). ``k_scale`` /
+    ``v_scale``: the row scales of an FP8 cache (module docstring): the token is stored
+    quantised and attended to in that form; the chunk default is then :data:`CHUNK_FP8`."""
     if qkv.dim() != 3 or qkv.shape[1] != 1:
         raise ValueError(f"decode_attention takes qkv [B, 1, 3C], got {tuple(qkv.shape)}")
     L_max = k_cache.shape[2]
     if pos is not None and pos + 1 > L_max:
         raise ValueError(f"decode_attention: position {pos} + 1 > cache length {L_max}")
-    if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache):
+    fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+    if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale):
         B, _, C3 = qkv.shape
         C = C3 // 3
         D = C // n_head
-        chunk = int(chunk or CHUNK)
+        chunk = int(chunk or (CHUNK_FP8 if fp8 else CHUNK))
         fused = FUSED_APPEND if fused is None else bool(fused)
         bound = L_max if len_bound is None else max(1, min(int(len_bound), L_max))
         if pos is not None and pos + 1 > bound:
@@ -190,6 +294,19 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
             raise ValueError(f"decode_attention: workspace of {workspace.numel()} fp32 < {need}")
         out = torch.empty(B, 1, C, dtype=qkv.dtype, device=qkv.device)
         lib, st = _lib.lib(), _lib.stream(qkv.device)
+        if fp8:
+            if not fused:
+                check(lib.dlbb_kv_append_fp8(qkv.data_ptr(), C3, k_cache.data_ptr(),
+                                             v_cache.data_ptr(), k_scale.data_ptr(),
+                                             v_scale.data_ptr(), length.data_ptr(), B, 1, n_head,
+                                             D, L_max, st), "kv_append_fp8")
+            check(lib.dlbb_attn_decode_fp8(qkv.data_ptr(), C3, k_cache.data_ptr(),
+                                           v_cache.data_ptr(), k_scale.data_ptr(),
+                                           v_scale.data_ptr(), length.data_ptr(),
+                                           workspace.data_ptr(), out.data_ptr(), C, B, n_head, D,
+                                           L_max, bound, chunk, int(fused), 1.0 / math.sqrt(D),
+                                           st), "attn_decode_fp8")
+            return out
         if not fused:
             check(lib.dlbb_kv_append(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(),
                                      length.data_ptr(), B, 1, n_head, D, L_max, st), "kv_append")
@@ -201,4 +318,4 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     p = _host_pos(length, pos)
     if p + 1 > L_max:
         raise ValueError(f"decode_attention: position {p} + 1 > cache length {L_max}")
-    return torch_decode_attention(qkv, n_head, k_cache, v_cache, p)
+    return torch_decode_attention(qkv, n_head, k_cache, v_cache, p, k_scale, v_scale)

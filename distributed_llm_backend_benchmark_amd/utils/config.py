@@ -31,6 +31,10 @@ Additions (all optional, defaults keep reference behaviour):
   hidden size and one rank's hidden and FFN widths to be multiples of 64, a batch of at most 16,
   and keeps both copies of the weights resident (+ 50 % weight memory). Not with ``gemm_dtype:
   fp8``.
+* ``execution.kv_cache_dtype``: ``bf16`` (default) | ``fp8`` — the KV cache of the decode steps
+  holds e4m3 codes with one fp32 scale per cached row of ``head_dim`` values (``ops.decode``;
+  ``run_tp --kv-cache``): ``head_dim + 4`` bytes per row instead of ``2 head_dim``. The appends
+  quantise, a decode step attends to the quantised rows; the prefill attention is unchanged.
 """
 
 from __future__ import annotations
@@ -63,6 +67,7 @@ DEFAULT_CONFIG: Dict[str, Any] = {
         "gemm_dtype": "bf16",
         "decode_tokens": 0,
         "decode_weight_dtype": "bf16",
+        "kv_cache_dtype": "bf16",
     },
     "system": {"omp_num_threads": 14, "mkl_num_threads": 14},
 }
@@ -138,6 +143,9 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
                           f"{ex['decode_weight_dtype']!r}")
     if ex["decode_weight_dtype"] == "fp8":
         check_w8_shapes(cfg, ws if isinstance(ws, int) else 1)
+    if ex["kv_cache_dtype"] not in ("bf16", "fp8"):
+        raise ConfigError("execution.kv_cache_dtype must be bf16|fp8, got "
+                          f"{ex['kv_cache_dtype']!r}")
     return cfg
 
 

@@ -13,6 +13,14 @@ Printed per candidate: microseconds per call and K / V bytes / time. The copy mo
 bytes twice (read + write), so its rate is given over 2x the bytes; ``share_of_copy`` is our
 read rate over that. ``--chunks`` adds our kernel at other split sizes, ``two_launch`` is the
 kv_append + attention form of the same step. Rows go to ``profiles/decode/attn_decode.jsonl``.
+
+``--fp8`` adds the FP8 (e4m3) KV cache beside it, same protocol and same process: ``ours_fp8`` is
+the decode step over caches holding the same K / V as e4m3 codes + one fp32 scale per row
+(``D + 4`` bytes per row; rotated over as many caches as the bf16 form), ``copy_fp8`` a device copy
+of exactly those code + scale bytes, ``ours_fp8_chunk<N>`` the kernel at the other ``--fp8-chunks``.
+``GBps`` of these candidates is over the bytes they actually read (``kv_bytes_fp8``);
+``fp8_over_bf16`` is ``us[ours_fp8] / us[ours]``, ``fp8_vs_bf16_max_rel_diff`` the output distance
+of the two cache types on the row's inputs.
 """
 
 from __future__ import annotations
@@ -67,6 +75,35 @@ def bench_row(B, H, D, L, args):
         if c != dec.CHUNK:
             cands[f"ours_chunk{c}"] = lambda i, c=c: ours(i, chunk=c)
 
+    kv_bytes_fp8 = 2 * B * H * L * (D + 4)
+    if args.fp8:
+        from distributed_llm_backend_benchmark_amd.ops import fp8
+
+        # the same K / V, quantised per row: codes [2, B, H, L, D] and scales [2, B, H, L]
+        caches8 = []
+        for kv in caches:
+            q8, s8 = fp8.quantize_rows(kv.reshape(-1, D))
+            caches8.append((q8.view(2, B, H, L, D), s8.view(2, B, H, L)))
+        sink8 = (torch.empty_like(caches8[0][0]), torch.empty_like(caches8[0][1]))
+        chunks8 = sorted(set(args.fp8_chunks))
+        ws8 = torch.empty(dec.workspace_numel(B, H, D, L, min(chunks8 + [dec.CHUNK_FP8])),
+                          dtype=torch.float32, device=dev)
+
+        def ours_fp8(i, **kw):
+            (kc, vc), (ks, vs) = caches8[i % nbuf]
+            return dec.decode_attention(qkv, H, kc, vc, length, workspace=ws8, k_scale=ks,
+                                        v_scale=vs, **kw)
+
+        def copy_fp8(i):
+            sink8[0].copy_(caches8[i % nbuf][0])
+            sink8[1].copy_(caches8[i % nbuf][1])
+
+        cands["ours_fp8"] = ours_fp8
+        cands["copy_fp8"] = copy_fp8
+        for c in chunks8:
+            if c != dec.CHUNK_FP8:
+                cands[f"ours_fp8_chunk{c}"] = lambda i, c=c: ours_fp8(i, chunk=c)
+
     graphs = {}
     for name, fn in cands.items():                       # warm every candidate, then capture
         for i in range(nbuf + 1):
@@ -97,11 +134,19 @@ def bench_row(B, H, D, L, args):
            "chunk": dec.CHUNK, "fused_append": dec.FUSED_APPEND, "inner": args.inner,
            "rounds": args.rounds, "us": us,
            "us_min": {n: min(v) for n, v in times.items()},
-           "GBps": {n: (2 if n == "copy" else 1) * kv_bytes / (t * 1e-6) / 1e9
+           "GBps": {n: (2 if n.startswith("copy") else 1)
+                    * (kv_bytes_fp8 if "fp8" in n else kv_bytes) / (t * 1e-6) / 1e9
                     for n, t in us.items()},
            "max_rel_diff_vs_sdpa": err}
     row["share_of_copy"] = row["GBps"]["ours"] / row["GBps"]["copy"]
     row["ours_over_sdpa"] = us["ours"] / us["sdpa"]
+    if args.fp8:
+        row["kv_bytes_fp8"] = kv_bytes_fp8
+        row["chunk_fp8"] = dec.CHUNK_FP8
+        row["share_of_copy_fp8"] = row["GBps"]["ours_fp8"] / row["GBps"]["copy_fp8"]
+        row["fp8_over_bf16"] = us["ours_fp8"] / us["ours"]
+        row["fp8_vs_bf16_max_rel_diff"] = float((ours_fp8(0).float() - ours(0).float()).abs().max()
+                                                / ref.abs().max())
     return row
 
 
@@ -110,6 +155,9 @@ def main(argv=None) -> int:
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rows", nargs="*", default=None, metavar="B,H,D,L")
     ap.add_argument("--chunks", type=int, nargs="*", default=[128, 256, 512])
+    ap.add_argument("--fp8", action="store_true",
+                    help="also time the FP8 (e4m3) KV cache: ours_fp8, copy_fp8, --fp8-chunks")
+    ap.add_argument("--fp8-chunks", type=int, nargs="*", default=[256, 512, 1024])
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--rotate-mb", type=int, default=512)
@@ -129,7 +177,9 @@ def main(argv=None) -> int:
                   f"{row['rotated_caches']} caches): " +
                   "  ".join(f"{n} {t:.1f} us ({row['GBps'][n]:.0f} GB/s)" for n, t in us.items())
                   + f"  share_of_copy {row['share_of_copy']:.2f}  ours/sdpa "
-                  f"{row['ours_over_sdpa']:.2f}", flush=True)
+                  f"{row['ours_over_sdpa']:.2f}" +
+                  (f"  fp8/bf16 {row['fp8_over_bf16']:.2f}  share_of_copy_fp8 "
+                   f"{row['share_of_copy_fp8']:.2f}" if args.fp8 else ""), flush=True)
     return 0
 
 
