@@ -1,37 +1,90 @@
-// Single-query (decode) attention over a KV cache, gfx950 (MI355X, CDNA4).
+// Single-query (decode) attention over a KV cache, bf16 or FP8 (OCP e4m3fn), gfx950 (MI355X,
+// CDNA4).
 //
-// Cache layout, per layer and rank: k_cache / v_cache [B, H, L_max, D] bf16, contiguous, so the
-// key stream of one (b, h) is one contiguous run; `length` is ONE device int32 = tokens already
+// Cache layout, per layer and rank: k_cache / v_cache [B, H, L_max, D], contiguous, so the key
+// stream of one (b, h) is one contiguous run; `length` is ONE device int32 = tokens already
 // cached, shared by the batch (and by every layer). Every kernel here reads it from device
 // memory, so a step captured in a HIP graph replays for successive positions.
 //
-//   kv_append_kernel           K / V rows of a fused qkv [B, T, 3, H, D] -> cache positions
+//   bf16 cache  rows of D bf16 (2 D bytes).
+//   FP8 cache   rows of D e4m3fn bytes and k_scale / v_scale [B, H, L_max] fp32: one scale per
+//               cached row, row ~= float(code) * scale (D + 4 bytes a row). A row is quantised
+//               exactly as gemm_fp8.hip's row quantiser does (ops.fp8): amax == 0 -> scale 1,
+//               bytes 0; otherwise inv = 448 / amax and scale = amax / 448 (IEEE fp32 divisions)
+//               and code = cvt_pk_fp8_f32(float(x) * inv), round to nearest even.
+//
+//   kv_append_kernel           K / V rows of a fused qkv [B, T, 3, H, D] bf16 -> cache positions
 //                              [length, length + T), 16-byte loads and stores.
+//   kv_append_fp8_kernel       the same rows -> codes and scales. One row lives in D / 8 lanes: a
+//                              16-byte load per lane, amax by shuffles, one convert pass, an
+//                              8-byte store of codes per lane.
 //   attn_decode_split_kernel   grid (n_chunks, H, B): workgroup (c, h, b) attends the one query
 //                              of (b, h) over keys [c * chunk, min((c + 1) * chunk, L)),
 //                              L = length + 1 (the cached tokens and the token being decoded),
 //                              and writes the partial (m, l, o[D]) in fp32 to the workspace.
 //   attn_decode_combine_kernel one workgroup per (b, h): merges the live chunks' partials in
-//                              chunk order and writes bf16 [B, 1, H * D] (heads interleaved).
+//                              chunk order and writes bf16 [B, 1, H * D] (heads interleaved). It
+//                              never reads the cache: one kernel for both formats.
 //
 // The split kernel is a bandwidth-bound read: K and V go from global memory straight into
-// VGPRs, 16 bytes per lane, D / 8 lanes per key (a wave reads 1 KiB of consecutive key rows per
-// load instruction); the dot product is reduced over those D / 8 lanes with shuffles. Each
-// group of D / 8 lanes (a "slot") keeps an online softmax of its own over the keys it walks
-// (fp32 running max m, sum l, and its 8 columns of o); slots are merged once at the end, inside
-// the wave by shuffles and across the 4 waves through LDS, in a fixed order. No MFMA, no LDS
-// staging of K / V, no atomics, no tickets: results are bit-identical from run to run.
+// VGPRs, 16 bytes per lane — 8 bf16 or 16 codes, so D / 8 or D / 16 lanes per key (a wave reads
+// 1 KiB of consecutive key rows per load instruction); the dot product is reduced over those
+// lanes with shuffles. Each such group of lanes (a "slot") keeps an online softmax of its own
+// over the keys it walks (fp32 running max m, sum l, and its 8 or 16 columns of o); slots are
+// merged once at the end, inside the wave by shuffles and across the 4 waves through LDS, in a
+// fixed order. No MFMA, no LDS staging of K / V, no atomics, no tickets: results are
+// bit-identical from run to run.
+//
+// FP8 codes are widened in registers (v_cvt_pk_f32_fp8, exact); the dot product runs on the raw
+// codes, the key's scale is folded into the score (s = dot * k_scale * scale_log2) and the
+// value's into the weight (o += (p * v_scale) * code, l += p).
 //
 // `fused` = 1: the chunk that owns position `length` takes the new token's K / V from `qkv` and
 // also writes them to the cache, so append + attend is one launch; 0: the caller appended first
-// (dlbb_kv_append) and every key is read from the cache.
+// (dlbb_kv_append / dlbb_kv_append_fp8) and every key is read from the cache. With the FP8 cache
+// the fused chunk quantises the token, stores codes + scales and attends to those codes, so the
+// step's result is attention over the cache contents after the append, exactly.
 #include "common.h"
 
 namespace dlbb {
 
+namespace {
+
 constexpr int kDecThreads = 256;
-constexpr int kDecUnroll = 4;          // keys in flight per slot (8 x 16 B loads per lane)
+constexpr int kDecUnroll = 4;          // keys in flight per slot (8 x 16 B loads per lane, + 8 scales)
 constexpr float kDecNegBig = -1.0e30f; // "no key yet": finite, so no inf - inf in the merges
+constexpr float kE4m3Max = 448.0f;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// 16 e4m3fn bytes (byte order) -> 16 floats, exactly
+__device__ __forceinline__ void e4m3x16_to_f32(const u32x4& r, float (&v)[16]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(r[i]), false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(r[i]), true);
+    v[4 * i] = lo[0];
+    v[4 * i + 1] = lo[1];
+    v[4 * i + 2] = hi[0];
+    v[4 * i + 3] = hi[1];
+  }
+}
+
+// 4 floats -> 4 e4m3fn bytes (byte order), round to nearest even
+__device__ __forceinline__ uint32_t f32x4_to_e4m3(float f0, float f1, float f2, float f3) {
+  int w = 0;
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(f0, f1, w, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(f2, f3, w, true);
+  return static_cast<uint32_t>(w);
+}
+
+// the row's scale and the multiplier of its elements, from the row's amax
+__device__ __forceinline__ void row_scale(float amax, float& inv, float& scale) {
+  const bool zero = amax == 0.f;
+  inv = zero ? 1.0f : kE4m3Max / amax;
+  scale = zero ? 1.0f : amax / kE4m3Max;
+}
 
 struct KvAppendArgs {
   const uint16_t* qkv;   // [B, T, 3, H, D], token row stride ld
@@ -68,10 +121,63 @@ __global__ __launch_bounds__(256) void kv_append_kernel(KvAppendArgs a) {
   }
 }
 
+struct KvAppend8Args {
+  const uint16_t* qkv;   // [B, T, 3, H, D], token row stride ld
+  uint8_t* k_cache;      // [B, H, L_max, D] e4m3fn
+  uint8_t* v_cache;
+  float* k_scale;        // [B, H, L_max]
+  float* v_scale;
+  const int* length;
+  int64_t ld;
+  int B, T, H, L_max;
+};
+
+// a row (b, t, k|v, h) of D bf16 per group of D / 8 lanes; uniform trip count over the grid, so
+// every lane of a group is active in the shuffles
+template <int D>
+__global__ __launch_bounds__(256) void kv_append_fp8_kernel(KvAppend8Args a) {
+  constexpr int LG = D / 8;                                 // lanes per row
+  const int len = *a.length;
+  const int64_t rows = static_cast<int64_t>(a.B) * a.T * 2 * a.H;
+  const int64_t step = static_cast<int64_t>(gridDim.x) * blockDim.x / LG;
+  const int piece = threadIdx.x % LG;
+  const int64_t first = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / LG;
+  for (int64_t r0 = 0; r0 < rows; r0 += step) {
+    const int64_t r = r0 + first;
+    const bool live = r < rows;
+    const int64_t rr = live ? r : 0;
+    const int64_t tok = rr / (2 * a.H);
+    const int kh = static_cast<int>(rr - tok * 2 * a.H);    // (k|v, h)
+    const int kv = kh / a.H, h = kh - kv * a.H;
+    const int b = static_cast<int>(tok / a.T), t = static_cast<int>(tok - (int64_t)b * a.T);
+    const u16x8 x = *reinterpret_cast<const u16x8*>(
+        a.qkv + tok * a.ld + static_cast<int64_t>(1 + kv) * a.H * D + h * D + piece * 8);
+    float f[8], amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      f[j] = bf16_to_f32(x[j]);
+      amax = __builtin_fmaxf(amax, __builtin_fabsf(f[j]));
+    }
+#pragma unroll
+    for (int off = 1; off < LG; off <<= 1) amax = __builtin_fmaxf(amax, __shfl_xor(amax, off, 64));
+    float inv, scale;
+    row_scale(amax, inv, scale);
+    const int64_t pos = static_cast<int64_t>(len) + t;
+    if (!live || len < 0 || pos >= a.L_max) continue;       // device-side guard: never past the cache
+    const int64_t dst = (static_cast<int64_t>(b) * a.H + h) * a.L_max + pos;
+    const u32x2 code{f32x4_to_e4m3(f[0] * inv, f[1] * inv, f[2] * inv, f[3] * inv),
+                     f32x4_to_e4m3(f[4] * inv, f[5] * inv, f[6] * inv, f[7] * inv)};
+    *reinterpret_cast<u32x2*>((kv ? a.v_cache : a.k_cache) + dst * D + piece * 8) = code;
+    if (piece == 0) (kv ? a.v_scale : a.k_scale)[dst] = scale;
+  }
+}
+
 struct DecodeArgs {
   const uint16_t* qkv;   // [B, 1, 3, H, D], batch row stride ld
-  uint16_t* k_cache;     // [B, H, L_max, D]
-  uint16_t* v_cache;
+  uint8_t* k_cache;      // [B, H, L_max, D] bf16 or e4m3fn
+  uint8_t* v_cache;
+  float* k_scale;        // [B, H, L_max]; null for the bf16 cache
+  float* v_scale;
   const int* length;
   float* ws;             // [B, H, n_chunks, D + 2]: m, l, o[D]
   uint16_t* out;         // [B, 1, H, D], batch row stride ldo
@@ -88,14 +194,57 @@ __device__ __forceinline__ int decode_keys(const DecodeArgs& a, int& len, bool& 
   return room ? len + 1 : a.L_max;
 }
 
-__device__ __forceinline__ void bf16x8_to_f32(const u16x8& r, float (&v)[8]) {
+// What differs between the cache formats: a lane's 16-byte fragment of a row (kCols columns of
+// Elem) and its widening to floats, and whether rows carry a scale.
+struct KvBf16 {
+  using Elem = uint16_t;
+  using Frag = u16x8;
+  static constexpr int kCols = 8;
+  static constexpr bool kScaled = false;
+  static __device__ __forceinline__ void widen(const Frag& r, float (&v)[8]) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = bf16_to_f32(r[j]);
+    for (int j = 0; j < 8; ++j) v[j] = bf16_to_f32(r[j]);
+  }
+};
+struct KvE4m3 {
+  using Elem = uint8_t;
+  using Frag = u32x4;
+  static constexpr int kCols = 16;
+  static constexpr bool kScaled = true;
+  static __device__ __forceinline__ void widen(const Frag& r, float (&v)[16]) {
+    e4m3x16_to_f32(r, v);
+  }
+};
+
+// 16 bf16 columns of a row held by LPK lanes -> the row's codes of these columns and its scale
+template <int LPK>
+__device__ __forceinline__ void quant_row16(const uint16_t* p, u32x4& code, float& scale) {
+  const u16x8 x0 = *reinterpret_cast<const u16x8*>(p);
+  const u16x8 x1 = *reinterpret_cast<const u16x8*>(p + 8);
+  float f[16], amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    f[j] = bf16_to_f32(x0[j]);
+    f[8 + j] = bf16_to_f32(x1[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) amax = __builtin_fmaxf(amax, __builtin_fabsf(f[j]));
+#pragma unroll
+  for (int off = 1; off < LPK; off <<= 1) amax = __builtin_fmaxf(amax, __shfl_xor(amax, off, 64));
+  float inv;
+  row_scale(amax, inv, scale);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    code[i] = f32x4_to_e4m3(f[4 * i] * inv, f[4 * i + 1] * inv, f[4 * i + 2] * inv,
+                            f[4 * i + 3] * inv);
 }
 
-template <int D>
+template <int D, typename Fmt>
 __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeArgs a) {
-  constexpr int LPK = D / 8;                 // lanes per key (16 B each)
+  using Elem = typename Fmt::Elem;
+  using Frag = typename Fmt::Frag;
+  constexpr int C = Fmt::kCols;              // columns per lane (16 B)
+  constexpr int LPK = D / C;                 // lanes per key
   constexpr int NS = kDecThreads / LPK;      // key slots per workgroup
   constexpr int U = kDecUnroll;
   __shared__ float red[kDecThreads / kWave][D + 2];
@@ -111,21 +260,69 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
   // position whose K / V come from qkv (and are stored to the cache here); -1: none
   const int newpos = (a.fused && room) ? len : -1;
 
-  const uint16_t* row = a.qkv + static_cast<int64_t>(b) * a.ld + h * D + sub * 8;
-  const uint16_t* nk = row + a.H * D;
-  const uint16_t* nv = row + 2 * a.H * D;
-  float q[8];
-  bf16x8_to_f32(*reinterpret_cast<const u16x8*>(row), q);
-  const int64_t base = (static_cast<int64_t>(b) * a.H + h) * a.L_max * D + sub * 8;
-  uint16_t* kc = a.k_cache + base;
-  uint16_t* vc = a.v_cache + base;
-
-  float m = kDecNegBig, l = 0.f, o[8];
+  // The compiler's schedule and register allocation of the whole kernel follow the statement
+  // order of this prologue and the way its address sums associate. Where the two formats differ
+  // below in nothing else, each keeps the order its measured kernel was built from
+  // (docs/PERFORMANCE.md, "One core for the bf16 and FP8 decode kernels").
+  const uint16_t* row = a.qkv + static_cast<int64_t>(b) * a.ld + h * D + sub * C;
+  // bf16: the token's K / V are read where the loop meets them, and copied to the cache there
+  [[maybe_unused]] const uint16_t *nkp = nullptr, *nvp = nullptr;
+  if constexpr (!Fmt::kScaled) {
+    nkp = row + a.H * D;
+    nvp = row + 2 * a.H * D;
+  }
+  float q[C];                                // the lane's C columns of the query
+  if constexpr (C == 8) {
+    KvBf16::widen(*reinterpret_cast<const u16x8*>(row), q);
+  } else {
+    const u16x8 q0 = *reinterpret_cast<const u16x8*>(row);
+    const u16x8 q1 = *reinterpret_cast<const u16x8*>(row + 8);
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = 0.f;
+    for (int j = 0; j < 8; ++j) {
+      q[j] = bf16_to_f32(q0[j]);
+      q[8 + j] = bf16_to_f32(q1[j]);
+    }
+  }
+  const int64_t rows = (static_cast<int64_t>(b) * a.H + h) * a.L_max;
+  // the lane's columns of row 0 of (b, h): cache + rows * D + sub * C
+  Elem *kc = reinterpret_cast<Elem*>(a.k_cache), *vc = reinterpret_cast<Elem*>(a.v_cache);
+  if constexpr (Fmt::kScaled) {
+    kc = kc + rows * D + sub * C;
+    vc = vc + rows * D + sub * C;
+  } else {
+    kc += rows * D + sub * C;
+    vc += rows * D + sub * C;
+  }
+
+  // FP8: the append, by the chunk owning `length` (workgroup-uniform): every slot holds the
+  // token's codes and scales, slot 0 stores them
+  [[maybe_unused]] float *ksc = nullptr, *vsc = nullptr;
+  [[maybe_unused]] Frag nk{}, nv{};
+  [[maybe_unused]] float nks = 1.f, nvs = 1.f;
+  if constexpr (Fmt::kScaled) {
+    ksc = a.k_scale + rows;
+    vsc = a.v_scale + rows;
+    if (newpos >= k0 && newpos < k1) {
+      quant_row16<LPK>(row + a.H * D, nk, nks);
+      quant_row16<LPK>(row + 2 * a.H * D, nv, nvs);
+      if (slot == 0) {
+        *reinterpret_cast<Frag*>(kc + static_cast<int64_t>(newpos) * D) = nk;
+        *reinterpret_cast<Frag*>(vc + static_cast<int64_t>(newpos) * D) = nv;
+        if (sub == 0) {
+          ksc[newpos] = nks;
+          vsc[newpos] = nvs;
+        }
+      }
+    }
+  }
+
+  float m = kDecNegBig, l = 0.f, o[C];
+#pragma unroll
+  for (int j = 0; j < C; ++j) o[j] = 0.f;
 
   for (int it = k0; it < k1; it += NS * U) {       // uniform trip count over the workgroup
-    u16x8 kr[U], vr[U];
+    Frag kr[U], vr[U];
+    [[maybe_unused]] float ks[U], vs[U];
     bool ok[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -133,23 +330,38 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
       ok[u] = key < k1;
       const int kk = ok[u] ? key : k1 - 1;         // masked slots re-read a live row
       const bool fresh = kk == newpos;
-      kr[u] = *reinterpret_cast<const u16x8*>(fresh ? nk : kc + static_cast<int64_t>(kk) * D);
-      vr[u] = *reinterpret_cast<const u16x8*>(fresh ? nv : vc + static_cast<int64_t>(kk) * D);
-      if (fresh && ok[u]) {                        // the append, by the chunk owning `length`
-        *reinterpret_cast<u16x8*>(kc + static_cast<int64_t>(kk) * D) = kr[u];
-        *reinterpret_cast<u16x8*>(vc + static_cast<int64_t>(kk) * D) = vr[u];
+      Elem* kp = kc + static_cast<int64_t>(kk) * D;
+      Elem* vp = vc + static_cast<int64_t>(kk) * D;
+      if constexpr (Fmt::kScaled) {
+        // row `newpos` is taken from the registers, never from what the loads below return for it
+        // (slot 0's stores may or may not have landed): the loads stay in bounds, kk < L <= L_max
+        const Frag kl = *reinterpret_cast<const Frag*>(kp);
+        const Frag vl = *reinterpret_cast<const Frag*>(vp);
+        const float ksl = ksc[kk], vsl = vsc[kk];
+        kr[u] = fresh ? nk : kl;
+        vr[u] = fresh ? nv : vl;
+        ks[u] = fresh ? nks : ksl;
+        vs[u] = fresh ? nvs : vsl;
+      } else {
+        kr[u] = *reinterpret_cast<const Frag*>(fresh ? nkp : kp);
+        vr[u] = *reinterpret_cast<const Frag*>(fresh ? nvp : vp);
+        if (fresh && ok[u]) {                      // the append, by the chunk owning `length`
+          *reinterpret_cast<Frag*>(kp) = kr[u];
+          *reinterpret_cast<Frag*>(vp) = vr[u];
+        }
       }
     }
     float s[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      float kf[8];
-      bf16x8_to_f32(kr[u], kf);
+      float kf[C];
+      Fmt::widen(kr[u], kf);
       float d = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], kf[j], d);
+      for (int j = 0; j < C; ++j) d = __builtin_fmaf(q[j], kf[j], d);
 #pragma unroll
       for (int off = 1; off < LPK; off <<= 1) d += __shfl_xor(d, off, 64);
+      if constexpr (Fmt::kScaled) d = d * ks[u];
       s[u] = ok[u] ? d * a.scale_log2 : kDecNegBig;
     }
     float mn = m;
@@ -158,15 +370,16 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
     const float alpha = __builtin_amdgcn_exp2f(m - mn);
     l *= alpha;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] *= alpha;
+    for (int j = 0; j < C; ++j) o[j] *= alpha;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const float p = ok[u] ? __builtin_amdgcn_exp2f(s[u] - mn) : 0.f;
-      float vf[8];
-      bf16x8_to_f32(vr[u], vf);
+      float p = ok[u] ? __builtin_amdgcn_exp2f(s[u] - mn) : 0.f;
+      float vf[C];
+      Fmt::widen(vr[u], vf);
       l += p;
+      if constexpr (Fmt::kScaled) p = p * vs[u];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = __builtin_fmaf(p, vf[j], o[j]);
+      for (int j = 0; j < C; ++j) o[j] = __builtin_fmaf(p, vf[j], o[j]);
     }
     m = mn;
   }
@@ -183,7 +396,7 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
     const float la = lo ? l * f1 : l2 * f2, lb = lo ? l2 * f2 : l * f1;
     l = la + lb;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < C; ++j) {
       const float o2 = __shfl_xor(o[j], off, 64);
       const float oa = lo ? o[j] * f1 : o2 * f2, ob = lo ? o2 * f2 : o[j] * f1;
       o[j] = oa + ob;
@@ -193,7 +406,7 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
   const int lane = tid & (kWave - 1), w = tid / kWave;
   if (lane < LPK) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) red[w][sub * 8 + j] = o[j];
+    for (int j = 0; j < C; ++j) red[w][sub * C + j] = o[j];
     if (sub == 0) {
       red[w][D] = m;
       red[w][D + 1] = l;
@@ -243,7 +456,52 @@ __global__ __launch_bounds__(D) void attn_decode_combine_kernel(DecodeArgs a) {
   a.out[static_cast<int64_t>(b) * a.ldo + h * D + d] = f32_to_bf16(acc / lsum);
 }
 
-static bool mis16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+bool mis(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; }
+
+// what all four entry points ask of qkv, the cache geometry and `length`
+bool qkv_cache_ok(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache,
+                  const void* length, int H, int D, int L_max) {
+  if (D != 64 && D != 128) return false;
+  if (L_max <= 0 || ld % 8 || ld < 3 * H * D || !length) return false;
+  return !(mis(qkv, 16) || mis(k_cache, 16) || mis(v_cache, 16));
+}
+
+// the FP8 cache's scale planes
+bool scales_ok(const void* k_scale, const void* v_scale) {
+  return k_scale && v_scale && !mis(k_scale, 4) && !mis(v_scale, 4);
+}
+
+// validation and the split + combine launches of both decode entry points
+template <typename Fmt>
+int decode_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, void* k_scale,
+                  void* v_scale, const void* length, void* ws, void* out, int64_t ldo, int B,
+                  int H, int D, int L_max, int len_bound, int chunk, int fused, float scale,
+                  hipStream_t stream) {
+  if (B <= 0 || H <= 0) return hipSuccess;
+  if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
+  if (chunk <= 0 || len_bound <= 0 || !ws || ldo < H * D) return hipErrorInvalidValue;
+  if (!k_cache || !v_cache || !out) return hipErrorInvalidValue;
+  if (Fmt::kScaled && !scales_ok(k_scale, v_scale)) return hipErrorInvalidValue;
+  if (H > 65535 || B > 65535) return hipErrorInvalidValue;
+  if (len_bound > L_max) len_bound = L_max;
+  const int n_chunks = (len_bound + chunk - 1) / chunk;
+  DecodeArgs a{static_cast<const uint16_t*>(qkv), static_cast<uint8_t*>(k_cache),
+               static_cast<uint8_t*>(v_cache), static_cast<float*>(k_scale),
+               static_cast<float*>(v_scale), static_cast<const int*>(length),
+               static_cast<float*>(ws), static_cast<uint16_t*>(out), ld, ldo, B, H, L_max, chunk,
+               n_chunks, fused ? 1 : 0, scale * 1.4426950408889634f};
+  const dim3 gs(n_chunks, H, B), gc(H, B);
+  if (D == 64) {
+    hipLaunchKernelGGL((attn_decode_split_kernel<64, Fmt>), gs, dim3(kDecThreads), 0, stream, a);
+    hipLaunchKernelGGL(attn_decode_combine_kernel<64>, gc, dim3(64), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL((attn_decode_split_kernel<128, Fmt>), gs, dim3(kDecThreads), 0, stream, a);
+    hipLaunchKernelGGL(attn_decode_combine_kernel<128>, gc, dim3(128), 0, stream, a);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
 
 }  // namespace dlbb
 
@@ -256,9 +514,7 @@ DLBB_API int dlbb_kv_append(const void* qkv, int64_t ld, void* k_cache, void* v_
                             const void* length, int B, int T, int H, int D, int L_max,
                             hipStream_t stream) {
   if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
-  if (D != 64 && D != 128) return hipErrorInvalidValue;
-  if (L_max <= 0 || ld % 8 || ld < 3 * H * D || !length) return hipErrorInvalidValue;
-  if (mis16(qkv) || mis16(k_cache) || mis16(v_cache)) return hipErrorInvalidValue;
+  if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
   KvAppendArgs a{static_cast<const uint16_t*>(qkv), static_cast<uint16_t*>(k_cache),
                  static_cast<uint16_t*>(v_cache), static_cast<const int*>(length), ld, B, T, H, D,
                  L_max};
@@ -267,34 +523,49 @@ DLBB_API int dlbb_kv_append(const void* qkv, int64_t ld, void* k_cache, void* v_
   return hipGetLastError();
 }
 
-// One decode step of attention: qkv [B, 1, 3, H, D] (batch row stride ld), the cache as above,
-// out [B, 1, H, D] bf16 (batch row stride ldo). Attends over *length + 1 keys; with fused != 0
-// the new token's K / V are taken from qkv and stored at position *length by the same launch,
-// else the caller has appended them already. ws: fp32 [B, H, n_chunks, D + 2], n_chunks =
+// The same for the FP8 cache: k_cache / v_cache [B, H, L_max, D] e4m3fn contiguous, k_scale /
+// v_scale [B, H, L_max] fp32 contiguous. Rows K / V of every token are quantised to cache
+// positions [*length, *length + T); positions >= L_max (and every position when *length < 0) are
+// dropped on the device.
+DLBB_API int dlbb_kv_append_fp8(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                void* k_scale, void* v_scale, const void* length, int B, int T,
+                                int H, int D, int L_max, hipStream_t stream) {
+  if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
+  if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
+  if (!k_cache || !v_cache || !scales_ok(k_scale, v_scale)) return hipErrorInvalidValue;
+  KvAppend8Args a{static_cast<const uint16_t*>(qkv), static_cast<uint8_t*>(k_cache),
+                  static_cast<uint8_t*>(v_cache), static_cast<float*>(k_scale),
+                  static_cast<float*>(v_scale), static_cast<const int*>(length), ld, B, T, H,
+                  L_max};
+  const int64_t lanes = static_cast<int64_t>(B) * T * 2 * H * (D / 8);
+  const dim3 grid(stream_grid(lanes, 256));
+  if (D == 64)
+    hipLaunchKernelGGL(kv_append_fp8_kernel<64>, grid, dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL(kv_append_fp8_kernel<128>, grid, dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// One decode step of attention: qkv [B, 1, 3, H, D] (batch row stride ld), the bf16 cache as
+// above, out [B, 1, H, D] bf16 (batch row stride ldo). Attends over *length + 1 keys; with
+// fused != 0 the new token's K / V are taken from qkv and stored at position *length by the same
+// launch, else the caller has appended them already. ws: fp32 [B, H, n_chunks, D + 2], n_chunks =
 // ceil(min(len_bound, L_max) / chunk); len_bound is the host's upper bound of *length + 1.
 DLBB_API int dlbb_attn_decode(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
                               const void* length, void* ws, void* out, int64_t ldo, int B, int H,
                               int D, int L_max, int len_bound, int chunk, int fused, float scale,
                               hipStream_t stream) {
-  if (B <= 0 || H <= 0) return hipSuccess;
-  if (D != 64 && D != 128) return hipErrorInvalidValue;
-  if (L_max <= 0 || chunk <= 0 || len_bound <= 0 || !length || !ws) return hipErrorInvalidValue;
-  if (ld % 8 || ld < 3 * H * D || ldo < H * D) return hipErrorInvalidValue;
-  if (mis16(qkv) || mis16(k_cache) || mis16(v_cache)) return hipErrorInvalidValue;
-  if (H > 65535 || B > 65535) return hipErrorInvalidValue;
-  if (len_bound > L_max) len_bound = L_max;
-  const int n_chunks = (len_bound + chunk - 1) / chunk;
-  DecodeArgs a{static_cast<const uint16_t*>(qkv), static_cast<uint16_t*>(k_cache),
-               static_cast<uint16_t*>(v_cache), static_cast<const int*>(length),
-               static_cast<float*>(ws), static_cast<uint16_t*>(out), ld, ldo, B, H, L_max, chunk,
-               n_chunks, fused ? 1 : 0, scale * 1.4426950408889634f};
-  const dim3 gs(n_chunks, H, B), gc(H, B);
-  if (D == 64) {
-    hipLaunchKernelGGL(attn_decode_split_kernel<64>, gs, dim3(kDecThreads), 0, stream, a);
-    hipLaunchKernelGGL(attn_decode_combine_kernel<64>, gc, dim3(64), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL(attn_decode_split_kernel<128>, gs, dim3(kDecThreads), 0, stream, a);
-    hipLaunchKernelGGL(attn_decode_combine_kernel<128>, gc, dim3(128), 0, stream, a);
-  }
-  return hipGetLastError();
+  return decode_launch<KvBf16>(qkv, ld, k_cache, v_cache, nullptr, nullptr, length, ws, out, ldo,
+                               B, H, D, L_max, len_bound, chunk, fused, scale, stream);
+}
+
+// The same over the FP8 cache: with fused != 0 the new token's K / V are quantised from qkv,
+// stored at position *length and attended to in their quantised form.
+DLBB_API int dlbb_attn_decode_fp8(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                  void* k_scale, void* v_scale, const void* length, void* ws,
+                                  void* out, int64_t ldo, int B, int H, int D, int L_max,
+                                  int len_bound, int chunk, int fused, float scale,
+                                  hipStream_t stream) {
+  return decode_launch<KvE4m3>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, ws, out, ldo,
+                               B, H, D, L_max, len_bound, chunk, fused, scale, stream);
 }

@@ -22,7 +22,7 @@ CPU tensors, ``DLBB_KERNELS=torch`` and other head dims use torch (:func:`torch_
 ``F.scaled_dot_product_attention`` on ``cache[:, :, :pos + 1]``. That path slices by the HOST
 position, so it is not replayable across positions in a captured graph.
 
-FP8 cache (opt-in, ``KVCache(kv_dtype="fp8")``; ``csrc/attn_decode_kv8.hip``). The contract:
+FP8 cache (opt-in, ``KVCache(kv_dtype="fp8")``; the same file's ``KvE4m3`` kernels). The contract:
 
 * ``k_cache`` / ``v_cache`` are ``[B, H_local, L_max, D]`` ``torch.float8_e4m3fn``, contiguous;
   ``k_scale`` / ``v_scale`` are ``[B, H_local, L_max]`` fp32, contiguous: one scale per cached
@@ -62,7 +62,7 @@ from .fp8 import E4M3, _quantize_torch
 # keys per workgroup of the split kernel (csrc/attn_decode.hip takes it per launch; the
 # alternatives measured are in docs/PERFORMANCE.md)
 CHUNK = 256
-# keys per workgroup of the FP8-cache split kernel (csrc/attn_decode_kv8.hip), a constant of its
+# keys per workgroup of the FP8-cache split kernel (csrc/attn_decode.hip too), a constant of its
 # own: a 256-key chunk holds half the bytes there. 256 / 512 / 1024 measured (docs/PERFORMANCE.md):
 # 512 is 10-15 % faster on the rows of >= 128 MiB of bf16 K + V and 6-32 % slower on the smaller
 # head-dim-128 ones, 1024 is 3-17 % faster from 256 MiB and up to 67 % slower below
@@ -221,6 +221,32 @@ def torch_decode_attention(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale
     return o.transpose(1, 2).reshape(B, 1, C3 // 3)
 
 
+def _hip_append(qkv, n_head: int, k_cache, v_cache, k_scale, v_scale, length, T: int) -> None:
+    """The HIP append of ``T`` tokens; the FP8 entry point when the cache has scales."""
+    B, _, C3 = qkv.shape
+    fp8 = k_scale is not None
+    scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
+    fn = _lib.lib().dlbb_kv_append_fp8 if fp8 else _lib.lib().dlbb_kv_append
+    check(fn(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(), *scales,
+             length.data_ptr(), B, T, n_head, C3 // 3 // n_head, k_cache.shape[2],
+             _lib.stream(qkv.device)), "kv_append_fp8" if fp8 else "kv_append")
+
+
+def _hip_decode(qkv, n_head: int, k_cache, v_cache, k_scale, v_scale, length, workspace, out,
+                bound: int, chunk: int, fused: bool) -> None:
+    """The HIP split + combine launches; the FP8 entry point when the cache has scales."""
+    B, _, C3 = qkv.shape
+    C = C3 // 3
+    D = C // n_head
+    fp8 = k_scale is not None
+    scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
+    fn = _lib.lib().dlbb_attn_decode_fp8 if fp8 else _lib.lib().dlbb_attn_decode
+    check(fn(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(), *scales,
+             length.data_ptr(), workspace.data_ptr(), out.data_ptr(), C, B, n_head, D,
+             k_cache.shape[2], bound, chunk, int(fused), 1.0 / math.sqrt(D),
+             _lib.stream(qkv.device)), "attn_decode_fp8" if fp8 else "attn_decode")
+
+
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
               length: torch.Tensor, pos: Optional[int] = None,
               k_scale: Optional[torch.Tensor] = None,
@@ -232,21 +258,9 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
     T, L_max = qkv.shape[1], k_cache.shape[2]
     if pos is not None and pos + T > L_max:
         raise ValueError(f"kv_append: position {pos} + {T} tokens > cache length {L_max}")
-    fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
-    if fp8 and use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale):
-        B, _, C3 = qkv.shape
-        check(_lib.lib().dlbb_kv_append_fp8(qkv.data_ptr(), C3, k_cache.data_ptr(),
-                                            v_cache.data_ptr(), k_scale.data_ptr(),
-                                            v_scale.data_ptr(), length.data_ptr(), B, T, n_head,
-                                            C3 // 3 // n_head, L_max, _lib.stream(qkv.device)),
-              "kv_append_fp8")
-        return
-    if not fp8 and use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache):
-        B, _, C3 = qkv.shape
-        check(_lib.lib().dlbb_kv_append(qkv.data_ptr(), C3, k_cache.data_ptr(),
-                                        v_cache.data_ptr(), length.data_ptr(), B, T, n_head,
-                                        C3 // 3 // n_head, L_max, _lib.stream(qkv.device)),
-              "kv_append")
+    _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+    if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale):
+        _hip_append(qkv, n_head, k_cache, v_cache, k_scale, v_scale, length, T)
         return
     p = _host_pos(length, pos)
     if p + T > L_max:
@@ -293,27 +307,10 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
         elif workspace.numel() < need or workspace.dtype != torch.float32:
             raise ValueError(f"decode_attention: workspace of {workspace.numel()} fp32 < {need}")
         out = torch.empty(B, 1, C, dtype=qkv.dtype, device=qkv.device)
-        lib, st = _lib.lib(), _lib.stream(qkv.device)
-        if fp8:
-            if not fused:
-                check(lib.dlbb_kv_append_fp8(qkv.data_ptr(), C3, k_cache.data_ptr(),
-                                             v_cache.data_ptr(), k_scale.data_ptr(),
-                                             v_scale.data_ptr(), length.data_ptr(), B, 1, n_head,
-                                             D, L_max, st), "kv_append_fp8")
-            check(lib.dlbb_attn_decode_fp8(qkv.data_ptr(), C3, k_cache.data_ptr(),
-                                           v_cache.data_ptr(), k_scale.data_ptr(),
-                                           v_scale.data_ptr(), length.data_ptr(),
-                                           workspace.data_ptr(), out.data_ptr(), C, B, n_head, D,
-                                           L_max, bound, chunk, int(fused), 1.0 / math.sqrt(D),
-                                           st), "attn_decode_fp8")
-            return out
         if not fused:
-            check(lib.dlbb_kv_append(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(),
-                                     length.data_ptr(), B, 1, n_head, D, L_max, st), "kv_append")
-        check(lib.dlbb_attn_decode(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(),
-                                   length.data_ptr(), workspace.data_ptr(), out.data_ptr(), C, B,
-                                   n_head, D, L_max, bound, chunk, int(fused),
-                                   1.0 / math.sqrt(D), st), "attn_decode")
+            _hip_append(qkv, n_head, k_cache, v_cache, k_scale, v_scale, length, 1)
+        _hip_decode(qkv, n_head, k_cache, v_cache, k_scale, v_scale, length, workspace, out,
+                    bound, chunk, fused)
         return out
     p = _host_pos(length, pos)
     if p + 1 > L_max:

@@ -19,7 +19,7 @@ GEMMs are untouched. On a GPU tensor the HIP kernels are the only implementation
 the kernel contract raises, there is no fall-back to bf16. The torch formulas below serve CPU
 tensors, ``DLBB_KERNELS=torch`` and ``kernels="torch"`` (the model-level reference).
 
-Weight-only FP8 for the decode step (``csrc/gemm_skinny_w8.hip``, :func:`linear_w8` /
+Weight-only FP8 for the decode step (``csrc/gemm_skinny.hip``, :func:`linear_w8` /
 :func:`w8_linear`): at M = batch rows <= 16 a linear is a pure stream of its weight, so the e4m3
 copy of the weight (the same cached ``quantize_weight`` entry) is streamed instead — half the
 bytes — widened to bf16 in registers (exact) and multiplied with the bf16 activation as it is;
@@ -292,7 +292,7 @@ def fp8_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
     return linear_fp8(xq, xs, wq, ws, bias, act, residual, out_dtype, out, kernels=kernels)
 
 
-# ---- weight-only FP8 (W8A16) for the decode step: csrc/gemm_skinny_w8.hip ----------------------
+# ---- weight-only FP8 (W8A16) for the decode step: csrc/gemm_skinny.hip -------------------------
 
 W8_LAUNCHES = {"count": 0}     # launches of the W8 skinny kernel itself
 

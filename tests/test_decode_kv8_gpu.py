@@ -1,4 +1,4 @@
-"""The FP8 (e4m3) KV-cache kernels (csrc/attn_decode_kv8.hip) against an fp32 softmax over the
+"""The FP8 (e4m3) KV-cache kernels (csrc/attn_decode.hip) against an fp32 softmax over the
 DEQUANTISED torch-quantised K / V (``ops.fp8._quantize_torch`` on the CPU), so both sides see the
 same codes and scales: every key position, slot and chunk edges, the device-side length, bit-exact
 quantising appends, determinism, HIP-graph replay across positions, the model's decode with

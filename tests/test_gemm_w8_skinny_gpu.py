@@ -1,4 +1,4 @@
-"""Weight-only FP8 (W8A16) skinny GEMM (``csrc/gemm_skinny_w8.hip``) on the GPU: exact integer
+"""Weight-only FP8 (W8A16) skinny GEMM (``csrc/gemm_skinny.hip``) on the GPU: exact integer
 products over every path of its plan, every e4m3 code dequantised exactly, the any-order fp32
 accumulation bound on random operands, every epilogue, padding rows / strides, determinism,
 graph capture, the contract refusals, and the decode step of the model and of ``run_tp`` on it.

@@ -3,7 +3,7 @@
 of the ``ops.linear`` dispatch whose contract holds (``mfma``, ``mfma_sk``, ``mfma_split``,
 ``blas`` = hipBLASLt) on the decode step's shapes, and against a bandwidth floor.
 
-``mfma_skinny_w8`` is the weight-only FP8 form of the skinny kernel (``csrc/gemm_skinny_w8.hip``,
+``mfma_skinny_w8`` is the weight-only FP8 form of the skinny kernel (``csrc/gemm_skinny.hip`` too,
 ``ops.fp8.linear_w8``): not a dispatch candidate (it changes numerics), timed beside the others on
 the e4m3 copy of the same weights, with its own floor ``copy_w8`` — the copy of the e4m3 bytes —
 and its ratio to ``mfma_skinny`` (the bytes say 0.5).
