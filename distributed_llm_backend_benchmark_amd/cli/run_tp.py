@@ -22,10 +22,11 @@ step replayed N times where the forward is capturable; ``--eager`` issues them f
 The record gets a ``decode`` section (``ms_per_token``, ``achieved_GBps``, ...) and the file name
 the suffix ``_decode<N>``. ``--decode-weights fp8`` streams the e4m3 copy of every linear's weight
 in those steps (weight-only FP8, bf16 activations): suffix ``_decode<N>_w8``, and the ``decode``
-section counts the streamed bytes. ``--kv-cache fp8`` keeps the KV cache of those steps as e4m3
-codes with one fp32 scale per cached row (``ops.decode``): suffix ``_kv8`` (after ``_w8``), the
+section counts the streamed bytes. ``--decode-weights mxfp4`` streams the MXFP4 copy (e2m1 codes,
+one e8m0 scale per 32 k; ``ops.mxfp4``) the same way: suffix ``_decode<N>_w4``. ``--kv-cache fp8`` keeps the KV cache of those steps as e4m3
+codes with one fp32 scale per cached row (``ops.decode``): suffix ``_kv8`` (after ``_w8`` / ``_w4``), the
 ``decode`` section carries ``kv_dtype`` and counts codes + scales in its cache and K / V bytes. It
-composes with ``--decode-weights fp8`` and needs decode tokens and a real attention (not ``slice``).
+composes with ``--decode-weights fp8`` / ``mxfp4`` and needs decode tokens and a real attention (not ``slice``).
 """
 
 from __future__ import annotations
@@ -96,11 +97,13 @@ def parse_args(argv=None):
                          "one at a time over a per-rank KV cache (execution.decode_tokens; 0 = "
                          "the prefill forward alone); adds a \"decode\" section to the record "
                          "and the suffix _decode<N> to the output file")
-    ap.add_argument("--decode-weights", choices=["bf16", "fp8"], default=None,
+    ap.add_argument("--decode-weights", choices=["bf16", "fp8", "mxfp4"], default=None,
                     help="with --decode: weight type the decode steps stream "
                          "(execution.decode_weight_dtype): fp8 = e4m3 with per-output-row scales "
                          "on the weight-only FP8 skinny GEMM, bf16 activations, batch <= 16; "
-                         "output file gets the suffix _w8")
+                         "output file gets the suffix _w8; mxfp4 = e2m1 codes with one e8m0 "
+                         "scale per 32 k on the weight-only MXFP4 skinny GEMM, the same limits, "
+                         "suffix _w4")
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default=None,
                     help="with --decode: storage of the KV cache (execution.kv_cache_dtype): fp8 = "
                          "e4m3 codes with one fp32 scale per cached row, head_dim + 4 bytes per "
@@ -173,6 +176,7 @@ def main(argv=None) -> int:
     if args.decode_weights:
         ex["decode_weight_dtype"] = args.decode_weights
     w8 = ex.get("decode_weight_dtype", "bf16") == "fp8"
+    w4 = ex.get("decode_weight_dtype", "bf16") == "mxfp4"
     if args.kv_cache:
         ex["kv_cache_dtype"] = args.kv_cache
     kv8 = ex.get("kv_cache_dtype", "bf16") == "fp8"
@@ -219,21 +223,23 @@ def main(argv=None) -> int:
                 print(f"ERROR: {e}")
             comm.destroy()
             return 1
-    if w8:
+    if w8 or w4:
         from ..ops import _lib
-        from ..utils.config import ConfigError, check_w8_shapes
+        from ..utils.config import ConfigError, check_w4_shapes, check_w8_shapes
 
+        wname, wkind, wgemm = ("fp8", "e4m3", "W8") if w8 else ("mxfp4", "MXFP4", "W4")
         hip = comm.is_gpu and ex.get("kernels", "hip") != "torch" and not _lib.force_torch()
         why = None
         if not n_dec:
-            why = ("--decode-weights fp8 (execution.decode_weight_dtype) needs decode tokens "
-                   "(--decode N): only the decode steps stream the e4m3 weights")
+            why = (f"--decode-weights {wname} (execution.decode_weight_dtype) needs decode "
+                   f"tokens (--decode N): only the decode steps stream the {wkind} weights")
         elif hip and int(config["input"]["batch_size"]) > 16:
-            why = (f"--decode-weights fp8: batch_size {config['input']['batch_size']} is larger "
-                   "than the 16 rows of the W8 skinny GEMM; there is no fall-back to bf16")
+            why = (f"--decode-weights {wname}: batch_size {config['input']['batch_size']} is "
+                   f"larger than the 16 rows of the {wgemm} skinny GEMM; there is no fall-back "
+                   "to bf16")
         else:
             try:                          # with the TP degree and model overrides now known
-                check_w8_shapes(config, eff_world)
+                (check_w8_shapes if w8 else check_w4_shapes)(config, eff_world)
             except ConfigError as e:
                 why = str(e)
         if why:
@@ -487,13 +493,16 @@ def main(argv=None) -> int:
         if extra["gemm_dtype"] != "bf16":      # never overwrites the bf16 record
             suffix += f"_{extra['gemm_dtype']}"
         if dec is not None:                    # never overwrites the prefill record
-            suffix += f"_decode{n_dec}" + ("_w8" if w8 else "") + ("_kv8" if kv8 else "")
+            suffix += f"_decode{n_dec}" + ("_w8" if w8 else "_w4" if w4 else "") + \
+                ("_kv8" if kv8 else "")
             d = results["decode"]
             print(f"  decode: {d['ms_per_token_mean']:.4f} ms/token ({d['timing_mode']}, "
                   f"attention {d['attention_path']}), {d['decode_tokens_per_s']:.0f} tokens/s, "
                   f"{d['achieved_GBps']:.0f} GB/s of weights + KV" +
                   (f" ({d['weight_dtype']} weights, {d['w8_launches_per_step']} W8 launches "
                    "per step)" if w8 else "") +
+                  (f" ({d['weight_dtype']} weights, {d['w4_launches_per_step']} W4 launches "
+                   "per step)" if w4 else "") +
                   (f" ({d['kv_dtype']} KV cache)" if kv8 else ""))
         out = os.path.join(config["experiment"]["output_dir"],
                            f"{args.backend}_{config['experiment']['name']}{suffix}.json")
@@ -517,7 +526,7 @@ class _DecodeRunner:
     def __init__(self, model, cache, comm, prompt: int, n: int, batch, capturable: bool, ex):
         import torch
 
-        from ..ops import _lib, fp8
+        from ..ops import _lib, fp8, mxfp4
         from ..ops import decode as dec_ops
 
         self.model, self.cache, self.comm = model, cache, comm
@@ -546,12 +555,14 @@ class _DecodeRunner:
         y = model(batch, kv_cache=cache)
         self.x.copy_(y[:, -1:])
         b0, l0 = model.comm_bytes(), fp8.W8_LAUNCHES["count"]
+        l4 = mxfp4.W4_LAUNCHES["count"]
         for _ in range(2):
             cache.set_length(prompt)
             self.step()
         comm.sync()
         self.allreduce_bytes_per_step = (model.comm_bytes() - b0) // 2
         self.w8_launches_per_step = (fp8.W8_LAUNCHES["count"] - l0) // 2
+        self.w4_launches_per_step = (mxfp4.W4_LAUNCHES["count"] - l4) // 2
         if not capturable:
             return
         if self.attention_path == "torch":
@@ -622,7 +633,9 @@ class _DecodeRunner:
         kv_mean = self.kv_per_key * (self.prompt + (self.n + 1) / 2.0)
         weights = self.model.get_memory_footprint()
         w8 = self.model.decode_weight_dtype == "fp8"
-        streamed = self.model.decode_weight_bytes()    # == weights unless the steps stream e4m3
+        w4 = self.model.decode_weight_dtype == "mxfp4"
+        # == weights unless the steps stream e4m3 or MXFP4
+        streamed = self.model.decode_weight_bytes()
         tuned = [t for t in gemm.kernel_mix()["linear"]["tuned"] if t["key"][0] == str(B)]
         by_choice = {}
         for t in tuned:
@@ -655,6 +668,10 @@ class _DecodeRunner:
             # step streams; weight_bytes_per_rank stays the resident bf16 footprint
             rec["weight_stream_bytes_per_rank"] = streamed
             rec["w8_launches_per_step"] = self.w8_launches_per_step
+        if w4:
+            # the code and block-scale bytes of every linear (+ the LayerNorm parameters)
+            rec["weight_stream_bytes_per_rank"] = streamed
+            rec["w4_launches_per_step"] = self.w4_launches_per_step
         return rec
 
 
@@ -713,7 +730,9 @@ def _check_against_dense(config, comm, model, batch) -> dict:
     # with one per token and rank, so the two differ by e4m3 rounding (2^-4 per element) carried
     # through every layer, not by bf16 rounding. decode_weight_dtype=fp8 gets the same tolerance:
     # wherever it applies the weights carry the same e4m3 rounding (the forwards compared here
-    # have no KV cache, so they run on the bf16 weights and sit far inside it)
+    # have no KV cache, so they run on the bf16 weights and sit far inside it).
+    # decode_weight_dtype=mxfp4 keeps the bf16 tolerance of 5e-2 for that very reason: the
+    # cache-less forwards compared here never touch the MXFP4 copy
     exe = config["execution"]
     fp8 = "fp8" in (exe.get("gemm_dtype", "bf16"), exe.get("decode_weight_dtype", "bf16"))
     tol = 0.25 if fp8 else 5e-2

@@ -22,6 +22,9 @@ per-token activation scales, per-output-row weight scales); the default stays bf
 ``decode_weight_dtype="fp8"`` (opt-in) streams the e4m3 copy of every linear's weight in those
 decode steps (``ops.w8_linear``, bf16 activations); prefill and cache-less forwards keep the bf16
 weights. Both copies are resident: + 50 % weight memory.
+``decode_weight_dtype="mxfp4"`` (opt-in) streams the MXFP4 copy instead (``ops.w4_linear``: e2m1
+codes, one e8m0 scale per 32 k — K/2 + K/32 bytes per row). Both copies are resident here too:
++ 26.6 % weight memory.
 ``kv_cache_dtype="fp8"`` (opt-in) makes ``new_kv_cache`` hold e4m3 codes with one fp32 scale per
 cached row (``ops.decode``): the appends quantise, a decode step attends to the quantised rows, the
 prefill attention itself stays on the bf16 ``qkv``.
@@ -231,12 +234,15 @@ class LLM(nn.Module):
         positions. ``attention="slice"`` (the stateless stub) gets one with no K / V storage:
         decode still runs, and measures the GEMMs and the ``[B, 1, H]`` all-reduces alone.
         With ``decode_weight_dtype="fp8"`` on the HIP path the batch is the M of the W8 skinny
-        GEMM: more than 16 rows raise here, not in the middle of a step. ``kv_cache_dtype``
-        picks the cache's storage (``"fp8"``: e4m3 codes + one fp32 scale per row)."""
-        if (self.decode_weight_dtype == "fp8" and batch > 16 and self.kernels != "torch"
+        GEMM (``"mxfp4"``: of the W4 one): more than 16 rows raise here, not in the middle of a
+        step. ``kv_cache_dtype`` picks the cache's storage (``"fp8"``: e4m3 codes + one fp32
+        scale per row)."""
+        if (self.decode_weight_dtype != "bf16" and batch > 16 and self.kernels != "torch"
                 and self.comm.device.type == "cuda" and not ops._lib.force_torch()):
-            raise ValueError(f"decode_weight_dtype='fp8': batch {batch} is larger than the 16 "
-                             "rows of the W8 skinny GEMM; there is no fall-back to bf16")
+            which = "W8" if self.decode_weight_dtype == "fp8" else "W4"
+            raise ValueError(f"decode_weight_dtype={self.decode_weight_dtype!r}: batch {batch} "
+                             f"is larger than the 16 rows of the {which} skinny GEMM; there is "
+                             "no fall-back to bf16")
         heads = self.num_heads // self.world_size
         layers = 0 if self.attention == "slice" else self.num_layers
         return ops.KVCache(layers, batch, heads, self.hidden_size // self.num_heads, max_len,
@@ -377,14 +383,16 @@ class LLM(nn.Module):
     def decode_weight_bytes(self) -> int:
         """Parameter bytes one decode step streams on this rank. ``decode_weight_dtype="fp8"``:
         every linear's N x K e4m3 bytes and its N fp32 row scales, plus the LayerNorm
-        parameters; ``"bf16"``: :meth:`get_memory_footprint`."""
-        if self.decode_weight_dtype != "fp8":
+        parameters; ``"mxfp4"``: every linear's N x K / 2 code bytes and N x K / 32 scale bytes,
+        plus the LayerNorm parameters; ``"bf16"``: :meth:`get_memory_footprint`."""
+        if self.decode_weight_dtype == "bf16":
             return self.get_memory_footprint()
+        w4 = self.decode_weight_dtype == "mxfp4"
         total = 0
         for m in self.modules():
             if isinstance(m, (ColumnParallelLinear, RowParallelLinear)):
                 n, k = m.weight.shape
-                total += n * k + 4 * n
+                total += n * k // 2 + n * k // 32 if w4 else n * k + 4 * n
             elif isinstance(m, LayerNormParams):
                 total += sum(p.numel() * p.element_size() for p in m.parameters())
         return total

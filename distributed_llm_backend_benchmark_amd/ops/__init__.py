@@ -5,6 +5,8 @@
 * :mod:`.gemm` — MFMA bf16 GEMM with fused bias / GELU / residual epilogues.
 * :mod:`.fp8` — e4m3 row quantiser and FP8 GEMM (block-scaled MFMA), the opt-in FP8 TP forward;
   the weight-only FP8 (W8A16) skinny GEMM of the opt-in FP8-weight decode step.
+* :mod:`.mxfp4` — MXFP4 (e2m1 codes, e8m0 block scales) weight quantiser and the weight-only
+  MXFP4 (W4A16) skinny GEMM of the opt-in MXFP4-weight decode step.
 * :mod:`.norm_act` — fused residual+LayerNorm and bias+GELU (fwd + bwd, autograd).
 * :mod:`.optim` — flat fused AdamW.
 * :mod:`.xent` — fused softmax cross-entropy on bf16 logits; LM-head-fused linear + loss.
@@ -19,6 +21,8 @@ from ._lib import available, loaded_path, KernelError
 from .elementwise import reduce_sum, cast, pack_rows, ChunkTable, ScaleTable, flatten_into
 from .gemm import linear
 from .fp8 import quantize_rows, linear_fp8, fp8_linear, linear_w8, w8_linear, W8_LAUNCHES
+from .mxfp4 import (quantize_mxfp4, dequantize_mxfp4, quantize_weight_mxfp4, linear_w4,
+                    w4_linear, w4_contract_error, w4_skinny_plan, W4_LAUNCHES)
 from .norm_act import layernorm, bias_gelu
 from .optim import FlatAdamW
 from .xent import cross_entropy, linear_cross_entropy
@@ -29,4 +33,6 @@ from .embedding import embedding
 __all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "CHUNK_FP8", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
            "ChunkTable", "ScaleTable", "flatten_into", "linear", "layernorm", "bias_gelu",
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
-           "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES"]
+           "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES",
+           "quantize_mxfp4", "dequantize_mxfp4", "quantize_weight_mxfp4", "linear_w4",
+           "w4_linear", "w4_contract_error", "w4_skinny_plan", "W4_LAUNCHES"]

@@ -80,6 +80,10 @@ _SIGS = {
     "dlbb_gemm_w8_nt_skinny": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                        c_int, c_int, c_int, c_void_p]),
+    "dlbb_gemm_w4_skinny_plan": (c_int, [c_int64, c_int64, c_int64, c_int, c_void_p]),
+    "dlbb_gemm_w4_nt_skinny": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                       c_int, c_int, c_int, c_void_p]),
     "dlbb_gemm_nt_phase_probe": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                          c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "dlbb_gemm_bf16_nn": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,

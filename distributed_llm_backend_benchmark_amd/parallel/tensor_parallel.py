@@ -20,6 +20,9 @@ MI355X design:
   a KV cache, M = batch rows) streams the e4m3 copy of the local weight through the weight-only
   FP8 skinny GEMM (``ops.w8_linear``: bf16 activation, row scale on the fp32 accumulator); every
   other call keeps the bf16 weight and today's dispatch. Both copies of the weight are resident.
+* ``decode_weight_dtype="mxfp4"`` (opt-in): the same routing with the MXFP4 copy of the local
+  weight (e2m1 codes, one e8m0 scale per 32 k) and the weight-only MXFP4 skinny GEMM
+  (``ops.w4_linear``).
 """
 
 from __future__ import annotations
@@ -35,6 +38,7 @@ from .comm import Comm
 
 
 GEMM_DTYPES = ("bf16", "fp8")
+DECODE_WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
 
 
 def _check_gemm_dtype(gemm_dtype: str) -> str:
@@ -44,12 +48,13 @@ def _check_gemm_dtype(gemm_dtype: str) -> str:
 
 
 def _check_decode_weight_dtype(decode_weight_dtype: str, gemm_dtype: str) -> str:
-    if decode_weight_dtype not in GEMM_DTYPES:
-        raise ValueError(f"decode_weight_dtype must be one of {GEMM_DTYPES}, got "
+    if decode_weight_dtype not in DECODE_WEIGHT_DTYPES:
+        raise ValueError(f"decode_weight_dtype must be one of {DECODE_WEIGHT_DTYPES}, got "
                          f"{decode_weight_dtype!r}")
-    if decode_weight_dtype == "fp8" and gemm_dtype == "fp8":
-        raise ValueError("decode_weight_dtype='fp8' cannot be combined with gemm_dtype='fp8' "
-                         "(the FP8 GEMM is not specified for the rows of a decode step)")
+    if decode_weight_dtype != "bf16" and gemm_dtype == "fp8":
+        raise ValueError(f"decode_weight_dtype={decode_weight_dtype!r} cannot be combined with "
+                         "gemm_dtype='fp8' (the FP8 GEMM is not specified for the rows of a "
+                         "decode step)")
     return decode_weight_dtype
 
 
@@ -82,6 +87,8 @@ class ColumnParallelLinear(nn.Module):
                 decode: bool = False) -> torch.Tensor:
         if decode and self.decode_weight_dtype == "fp8":
             return ops.w8_linear(x, self.weight, act=act, kernels=self.kernels)
+        if decode and self.decode_weight_dtype == "mxfp4":
+            return ops.w4_linear(x, self.weight, act=act, kernels=self.kernels)
         if self.gemm_dtype == "fp8":
             return ops.fp8_linear(x, self.weight, act=act, kernels=self.kernels)
         if self.kernels == "torch":
@@ -224,12 +231,15 @@ class RowParallelLinear(nn.Module):
         per micro-batch in flight). With a registered output, ``y`` is a view of a buffer shared
         by every same-shape row-parallel layer: consume it before the next row-parallel call.
         ``decode``: a one-token step; with ``decode_weight_dtype="fp8"`` the GEMM streams the
-        e4m3 weight (fp32-wire and registered-output variants included)."""
+        e4m3 weight, with ``"mxfp4"`` the MXFP4 one (fp32-wire and registered-output variants
+        included)."""
         fp32_wire = self.allreduce_dtype == "fp32"
         fp8 = self.gemm_dtype == "fp8"
         w8 = decode and self.decode_weight_dtype == "fp8"
+        w4 = decode and self.decode_weight_dtype == "mxfp4"
         if self.kernels == "torch":
             y = (ops.w8_linear(x, self.weight, kernels="torch") if w8
+                 else ops.w4_linear(x, self.weight, kernels="torch") if w4
                  else ops.fp8_linear(x, self.weight, kernels="torch") if fp8
                  else x @ self.weight.t())
             if fp32_wire:
@@ -243,12 +253,16 @@ class RowParallelLinear(nn.Module):
             y = buf.view(*x.shape[:-1], self.out_features)
             if w8:
                 ops.w8_linear(x, self.weight, out_dtype=odt, out=y)
+            elif w4:
+                ops.w4_linear(x, self.weight, out_dtype=odt, out=y)
             elif fp8:
                 ops.fp8_linear(x, self.weight, out_dtype=odt, out=y)
             else:
                 ops.linear(x, self.weight, out_dtype=odt, out=y)
         elif w8:
             y = ops.w8_linear(x, self.weight, out_dtype=odt)
+        elif w4:
+            y = ops.w4_linear(x, self.weight, out_dtype=odt)
         elif fp8:
             y = ops.fp8_linear(x, self.weight, out_dtype=odt)
         else:

@@ -25,12 +25,15 @@ Additions (all optional, defaults keep reference behaviour):
 * ``execution.gemm_dtype``: ``bf16`` (default) | ``fp8`` — the TP linears quantise activations
   per token and weights per output row to e4m3 and run the FP8 GEMM (``ops.fp8``); needs the
   hidden and FFN widths of one rank's shard to be multiples of 128.
-* ``execution.decode_weight_dtype``: ``bf16`` (default) | ``fp8`` — the one-token decode steps
+* ``execution.decode_weight_dtype``: ``bf16`` (default) | ``fp8`` | ``mxfp4`` — the one-token
+  decode steps
   (``decode_tokens``) stream every linear's weight as e4m3 with one scale per output row through
   the weight-only FP8 skinny GEMM (bf16 activations; ``run_tp --decode-weights``); needs the
   hidden size and one rank's hidden and FFN widths to be multiples of 64, a batch of at most 16,
-  and keeps both copies of the weights resident (+ 50 % weight memory). Not with ``gemm_dtype:
-  fp8``.
+  and keeps both copies of the weights resident (+ 50 % weight memory). ``mxfp4`` streams e2m1
+  codes with one e8m0 scale per 32 k through the weight-only MXFP4 skinny GEMM instead
+  (``ops.mxfp4``): those widths must be multiples of 128, the batch at most 16, + 26.6 % weight
+  memory. Neither with ``gemm_dtype: fp8``.
 * ``execution.kv_cache_dtype``: ``bf16`` (default) | ``fp8`` — the KV cache of the decode steps
   holds e4m3 codes with one fp32 scale per cached row of ``head_dim`` values (``ops.decode``;
   ``run_tp --kv-cache``): ``head_dim + 4`` bytes per row instead of ``2 head_dim``. The appends
@@ -138,11 +141,13 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
         raise ConfigError(f"execution.gemm_dtype must be bf16|fp8, got {ex['gemm_dtype']!r}")
     if ex["gemm_dtype"] == "fp8":
         check_fp8_shapes(cfg, ws if isinstance(ws, int) else 1)
-    if ex["decode_weight_dtype"] not in ("bf16", "fp8"):
-        raise ConfigError("execution.decode_weight_dtype must be bf16|fp8, got "
+    if ex["decode_weight_dtype"] not in ("bf16", "fp8", "mxfp4"):
+        raise ConfigError("execution.decode_weight_dtype must be bf16|fp8|mxfp4, got "
                           f"{ex['decode_weight_dtype']!r}")
     if ex["decode_weight_dtype"] == "fp8":
         check_w8_shapes(cfg, ws if isinstance(ws, int) else 1)
+    if ex["decode_weight_dtype"] == "mxfp4":
+        check_w4_shapes(cfg, ws if isinstance(ws, int) else 1)
     if ex["kv_cache_dtype"] not in ("bf16", "fp8"):
         raise ConfigError("execution.kv_cache_dtype must be bf16|fp8, got "
                           f"{ex['kv_cache_dtype']!r}")
@@ -178,6 +183,23 @@ def check_w8_shapes(config: Dict[str, Any], world: int) -> None:
         if width % world or (width // world) % 64:
             raise ConfigError(f"execution.decode_weight_dtype=fp8 needs model.{key} / {world} "
                               f"ranks to be a multiple of 64, got {width} / {world}")
+
+
+def check_w4_shapes(config: Dict[str, Any], world: int) -> None:
+    """The weight-only MXFP4 skinny GEMM of the decode steps reduces over units of 128 (four MX
+    blocks) and writes tiles of 16 output columns: the hidden size and the per-rank shard widths
+    ``hidden_size / world`` and ``ffn_intermediate / world`` must be multiples of 128; every
+    per-rank output width is then a multiple of 16 as well. ``world`` as in
+    :func:`check_fp8_shapes`."""
+    m = config["model"]
+    hidden, ffn = int(m["hidden_size"]), int(m["ffn_intermediate"])
+    if hidden % 128:
+        raise ConfigError("execution.decode_weight_dtype=mxfp4 needs model.hidden_size to be a "
+                          f"multiple of 128, got {hidden}")
+    for key, width in (("hidden_size", hidden), ("ffn_intermediate", ffn)):
+        if width % world or (width // world) % 128:
+            raise ConfigError(f"execution.decode_weight_dtype=mxfp4 needs model.{key} / {world} "
+                              f"ranks to be a multiple of 128, got {width} / {world}")
 
 
 def load_config(config_path: str) -> Dict[str, Any]:

@@ -8,6 +8,11 @@ of the ``ops.linear`` dispatch whose contract holds (``mfma``, ``mfma_sk``, ``mf
 the e4m3 copy of the same weights, with its own floor ``copy_w8`` — the copy of the e4m3 bytes —
 and its ratio to ``mfma_skinny`` (the bytes say 0.5).
 
+``mfma_skinny_w4`` is the weight-only MXFP4 form (``ops.mxfp4.linear_w4``), timed the same way on
+the MXFP4 copy of the same weights (e2m1 codes + one e8m0 scale per 32 k: 0.266 of the bf16
+bytes), with its floor ``copy_w4`` — the copy of exactly the code and scale bytes — and its ratios
+to ``mfma_skinny_w8`` (the bytes say 0.53) and to ``mfma_skinny``.
+
 Rows: the sixteen M = 8 shapes of the 7B decode step (four each at world 1 and on rank 0's shard
 of a 2-, 4- and 8-way run) plus the shard-8 QKV shape at M = 1 and M = 16. ``--candidates``
 restricts what is timed (``mfma_skinny`` and the copies always are).
@@ -18,7 +23,7 @@ back-to-back calls, median of ``--rounds`` (9) alternating rounds, twice:
 * **cold**: the calls rotate over enough distinct copies of W to exceed the 256 MiB last-level
   cache (``--rotate-mb``; as many 10-call graphs as it takes to walk all copies, replayed in
   turn), as the 32 layers of a decode step do; the e4m3 weights are half the size, so there are
-  twice as many of them;
+  twice as many of them, and as many MXFP4 ones as exceed the same bytes;
 * **warm**: one W, as the autotuner times its candidates.
 
 The floor is ``dst.copy_(src)`` of the same W bytes. The copy moves the bytes twice (read +
@@ -57,6 +62,7 @@ DEFAULT_ROWS = [("w1 qkv", 8, 12288, 4096), ("w1 out", 8, 4096, 4096),
 
 
 W8 = "mfma_skinny_w8"
+W4 = "mfma_skinny_w4"
 
 
 def candidates(gemm, x, w, out, only=None):
@@ -110,7 +116,7 @@ def _time(torch, graph_sets, inner, rounds):
 def bench_row(label, M, N, K, args):
     import torch
 
-    from distributed_llm_backend_benchmark_amd.ops import fp8, gemm
+    from distributed_llm_backend_benchmark_amd.ops import fp8, gemm, mxfp4
 
     dev = torch.device("cuda", 0)
     w_bytes = N * K * 2
@@ -123,6 +129,7 @@ def bench_row(label, M, N, K, args):
     sink = torch.empty_like(ws[0])
     names = candidates(gemm, x, ws[0], out, args.candidates)
     with_w8 = args.candidates is None or W8 in args.candidates
+    with_w4 = (args.candidates is None or W4 in args.candidates) and K % 128 == 0
     before = gemm.SKINNY_LAUNCHES["count"]
     ref = x.float() @ ws[0].float().t()
     errs = {}
@@ -141,6 +148,25 @@ def bench_row(label, M, N, K, args):
         assert fp8.W8_LAUNCHES["count"] == before + 1
         errs[W8] = float((out.float() - ref).norm() / ref.norm())
 
+    nbuf4, w4_bytes = 0, N * K // 2 + N * K // 32
+    if with_w4:
+        # MXFP4 copies of the same weights, each one flat buffer (codes, then scales) so that
+        # copy_w4 moves exactly the bytes the kernel streams
+        nbuf4 = max(1, -(-args.rotate_mb * (1 << 20) // w4_bytes))
+        q4 = []
+        for i in range(nbuf4):
+            if i < nbuf:
+                c, sc = mxfp4.quantize_mxfp4(ws[i])
+                flat = torch.cat([c.view(-1), sc.view(-1)])
+            else:
+                flat = q4[i % nbuf][0].clone()
+            q4.append((flat, flat[:N * K // 2].view(N, K // 2), flat[N * K // 2:].view(N, K // 32)))
+        sink4 = torch.empty_like(q4[0][0])
+        before = mxfp4.W4_LAUNCHES["count"]
+        mxfp4.linear_w4(x, q4[0][1], q4[0][2], out=out)
+        assert mxfp4.W4_LAUNCHES["count"] == before + 1
+        errs[W4] = float((out.float() - ref).norm() / ref.norm())
+
     def call(n):
         f = gemm._IMPLS[n]
         return lambda i: f(x, ws[i % nbuf], None, None, None, out, None)
@@ -152,6 +178,10 @@ def bench_row(label, M, N, K, args):
         fns[W8] = lambda i: fp8.linear_w8(x, *q8[i % nbuf8], out=out)
         fns["copy_w8"] = lambda i: sink8.copy_(q8[i % nbuf8][0])
         walk[W8] = walk["copy_w8"] = nbuf8
+    if with_w4:
+        fns[W4] = lambda i: mxfp4.linear_w4(x, q4[i % nbuf4][1], q4[i % nbuf4][2], out=out)
+        fns["copy_w4"] = lambda i: sink4.copy_(q4[i % nbuf4][0])
+        walk[W4] = walk["copy_w4"] = nbuf4
     cold = _time(torch, {n: _graphs(torch, f, walk[n], args.inner) for n, f in fns.items()},
                  args.inner, args.rounds)
     warm = _time(torch, {n: _graphs(torch, (lambda i, f=f: f(0)), 1, args.inner)
@@ -159,6 +189,8 @@ def bench_row(label, M, N, K, args):
     del ws, sink
     if with_w8:
         del q8, sink8
+    if with_w4:
+        del q4, sink4
     plan = gemm.skinny_plan(M, N, K, gemm._num_cus(dev))
     row = {"row": label, "M": M, "N": N, "K": K, "w_bytes": w_bytes, "rotated_weights": nbuf,
            "inner": args.inner, "rounds": args.rounds,
@@ -185,10 +217,24 @@ def bench_row(label, M, N, K, args):
                 w8_GBps=round(w_bytes / 2 / med[W8] / 1e3, 1),
                 copy_w8_GBps_2x_bytes=round(w_bytes / med["copy_w8"] / 1e3, 1),
                 w8_share_of_copy=round(med["copy_w8"] / (2 * med[W8]), 3))
+        if with_w4:
+            # the W4 kernel: its code + scale read rate, the copy of those bytes (moved twice),
+            # and its time over the W8 and the bf16 skinny kernels' in the same rounds
+            row[tag].update(
+                w4_over_skinny=round(med[W4] / med["mfma_skinny"], 3),
+                w4_GBps=round(w4_bytes / med[W4] / 1e3, 1),
+                copy_w4_GBps_2x_bytes=round(2 * w4_bytes / med["copy_w4"] / 1e3, 1),
+                w4_share_of_copy=round(med["copy_w4"] / (2 * med[W4]), 3))
+            if with_w8:
+                row[tag]["w4_over_w8"] = round(med[W4] / med[W8], 3)
     if with_w8:
         p8 = fp8.w8_skinny_plan(M, N, K, gemm._num_cus(dev))
         row["w8_bytes"], row["rotated_weights_w8"] = w_bytes // 2, nbuf8
         row["plan_w8"] = {"grid": p8[0], "k_split_in_workgroup": p8[1]}
+    if with_w4:
+        p4 = mxfp4.w4_skinny_plan(M, N, K, gemm._num_cus(dev))
+        row["w4_bytes"], row["rotated_weights_w4"] = w4_bytes, nbuf4
+        row["plan_w4"] = {"grid": p4[0], "k_split_in_workgroup": p4[1]}
     return row
 
 
@@ -199,7 +245,8 @@ def _ratio(t) -> str:
 
 
 def summary(rows) -> str:
-    cols = ["mfma_skinny", W8, "mfma", "mfma_sk", "mfma_split", "blas", "copy", "copy_w8"]
+    cols = ["mfma_skinny", W8, W4, "mfma", "mfma_sk", "mfma_split", "blas", "copy", "copy_w8",
+            "copy_w4"]
     lines = ["# Skinny-M GEMM table (`tools/skinny_gemm_table.py`)", "",
              "µs per call (HIP graph of 10 calls, median of 9 alternating rounds). cold = calls "
              "rotate over > 256 MiB of distinct weights; warm = one weight. copy = "
@@ -207,13 +254,16 @@ def summary(rows) -> str:
              "plan = workgroups x waves per workgroup (K-split inside the workgroup). "
              f"{W8} = the weight-only FP8 skinny kernel on the e4m3 copy of W (half the bytes; "
              "copy_w8 = the copy of those); W8 / skinny = its time over mfma_skinny's; W8 share = "
-             "its e4m3 read rate over copy_w8's rate.", ""]
+             "its e4m3 read rate over copy_w8's rate. "
+             f"{W4} = the weight-only MXFP4 skinny kernel on the MXFP4 copy of W (0.266 of the "
+             "bytes: codes + block scales; copy_w4 = the copy of exactly those); W4 / W8 and W4 / "
+             "skinny = its time over theirs; W4 share = its read rate over copy_w4's rate.", ""]
     for tag in ("cold", "warm"):
         lines += [f"## {tag}", "",
                   "| row | M, N, K | W | plan | " + " | ".join(cols) +
                   " | skinny / best other | skinny GB/s | copy GB/s | fastest | W8 / skinny | "
-                  "W8 GB/s | W8 share |",
-                  "|" + "---|" * (len(cols) + 11)]
+                  "W8 GB/s | W8 share | W4 / W8 | W4 / skinny | W4 GB/s | W4 share |",
+                  "|" + "---|" * (len(cols) + 15)]
         for r in rows:
             t = r[tag]
             us = " | ".join(f"{t['us'][c]:.1f}" if c in t["us"] else "n/a" for c in cols)
@@ -223,7 +273,11 @@ def summary(rows) -> str:
                 f"{_ratio(t)} | {t['skinny_GBps']:.0f} | "
                 f"{t['copy_GBps_2x_bytes']:.0f} | {t['fastest']} | " +
                 (f"{t['w8_over_skinny']:.2f} | {t['w8_GBps']:.0f} | {t['w8_share_of_copy']:.2f} |"
-                 if "w8_over_skinny" in t else "n/a | n/a | n/a |"))
+                 if "w8_over_skinny" in t else "n/a | n/a | n/a |") +
+                ((f" {t['w4_over_w8']:.2f} |" if "w4_over_w8" in t else " n/a |") +
+                 f" {t['w4_over_skinny']:.2f} | {t['w4_GBps']:.0f} | "
+                 f"{t['w4_share_of_copy']:.2f} |"
+                 if "w4_over_skinny" in t else " n/a | n/a | n/a | n/a |"))
         lines.append("")
     diff = [r["row"] for r in rows if r["cold"]["fastest"] != r["warm"]["fastest"]]
     lines.append("Rows whose cold and warm rankings name a different fastest candidate: "
@@ -286,7 +340,7 @@ def main(argv=None) -> int:
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--rotate-mb", type=int, default=320)
     ap.add_argument("--candidates", nargs="*", default=None, metavar="NAME",
-                    help=f"time only these beside mfma_skinny and the copies (e.g. {W8})")
+                    help=f"time only these beside mfma_skinny and the copies (e.g. {W8} {W4})")
     ap.add_argument("--out-dir", default=os.path.join(REPO, "profiles", "skinny_gemm"))
     ap.add_argument("--pmc-loop", type=int, default=0, metavar="N")
     ap.add_argument("--pmc-csv", nargs="+", default=None, metavar="FILE")
@@ -315,7 +369,10 @@ def main(argv=None) -> int:
                       f" us | skinny {t['skinny_GBps']:.0f} GB/s, copy "
                       f"{t['copy_GBps_2x_bytes']:.0f} GB/s, skinny/best other {_ratio(t)}" +
                       (f", W8/skinny {t['w8_over_skinny']:.2f}, W8 share of its copy "
-                       f"{t['w8_share_of_copy']:.2f}" if "w8_over_skinny" in t else ""),
+                       f"{t['w8_share_of_copy']:.2f}" if "w8_over_skinny" in t else "") +
+                      (f", W4/W8 {t.get('w4_over_w8', float('nan')):.2f}, W4/skinny "
+                       f"{t['w4_over_skinny']:.2f}, W4 share of its copy "
+                       f"{t['w4_share_of_copy']:.2f}" if "w4_over_skinny" in t else ""),
                       flush=True)
     with open(os.path.join(args.out_dir, "SUMMARY.md"), "w") as f:
         f.write(summary(done))
