@@ -69,6 +69,9 @@ def parse_args(argv=None):
                          "after backward and the exposed comm time (stream-issued reductions)")
     ap.add_argument("--zero", action="store_true",
                     help="ZeRO-2-style: reduce-scatter grads, sharded AdamW, all-gather params")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="F",
+                    help="clip the global L2 norm of the averaged gradient at F on the device "
+                         "(off by default); the result then reports the norms")
     ap.add_argument("--compare-overlap", action="store_true")
     ap.add_argument("--graph", action="store_true",
                     help="capture the whole training step in a HIP graph after warmup and replay "
@@ -127,14 +130,16 @@ def run(args, comm, overlap: bool):
     if args.zero:
         from ..parallel.zero import ShardedTrainer
 
-        tr = ShardedTrainer(model, comm, lr=args.lr, bucket_mb=args.bucket_mb, overlap=overlap)
+        tr = ShardedTrainer(model, comm, lr=args.lr, bucket_mb=args.bucket_mb, overlap=overlap,
+                            clip_grad_norm=args.clip_grad_norm)
     else:
         tr = FlatParamTrainer(model, comm if comm.world_size > 1 else None, lr=args.lr,
                               bucket_mb=args.bucket_mb, overlap=overlap, mode=args.mode,
                               allreduce=args.allreduce, comm_blocks=args.comm_blocks,
                               emulate_comm=args.emulate_comm, emulate_world=args.emulate_world,
                               late_bucket=not args.no_late_bucket,
-                              split_optimizer=not args.no_split_optimizer)
+                              split_optimizer=not args.no_split_optimizer,
+                              clip_grad_norm=args.clip_grad_norm)
     # everything after the trainer registered its buckets runs under try/finally, so
     # a failure (an agreed one: check_comm_errors, a section's candidate) still releases the IPC
     # registrations and gradient buffers before the caller moves on to the next candidate
@@ -159,12 +164,15 @@ def _train(args, comm, tr, model, cfg):
         tr.opt.lr = args.lr * min(1.0, (tr.step_count + 1) / max(1, args.lr_warmup))
 
     first_loss = None
+    first_norm = None
     for i in range(args.warmup):
         x, y = data.get_batch()
         set_lr()
         out = tr.step(x, y, sync_loss=(i == 0))
         if i == 0:
             first_loss = out
+            if args.clip_grad_norm is not None:     # beside the loss sync, outside the timing
+                first_norm = tr.last_grad_norm()
 
     def step_fn(x, y):
         set_lr()
@@ -218,6 +226,10 @@ def _train(args, comm, tr, model, cfg):
         tr.save_checkpoint(args.save_checkpoint)
         res["checkpoint"] = args.save_checkpoint
     res["step_count"] = tr.step_count
+    if args.clip_grad_norm is not None:         # only with clipping on: read after the final sync
+        res["clip_grad_norm"] = args.clip_grad_norm
+        res["grad_norm_first_step"] = first_norm
+        res["grad_norm_last"] = tr.last_grad_norm()
     return res
 
 
@@ -242,16 +254,15 @@ def main(argv=None) -> int:
                                                        priority=args.main_stream_priority))
     with tracing.torch_profile(args.torch_profile, comm.rank), main_ctx:
         main_res = run(args, comm, overlap=not args.no_overlap)
+    config_keys = ("n_layer", "n_head", "n_embd", "vocab", "batch", "seq", "bucket_mb", "mode",
+                   "allreduce", "zero", "comm_blocks", "emulate_comm", "emulate_world",
+                   "no_late_bucket", "no_split_optimizer", "main_stream_priority")
+    if args.clip_grad_norm is not None:         # off: the record stays what it always was
+        config_keys += ("clip_grad_norm",)
     out = {"metric": "gpt2_ddp_tokens_per_s", "value": main_res["tokens_per_s"],
            "n_gpus": comm.world_size, "overlap": not args.no_overlap, **main_res,
            "host_affinity_per_rank": affinity,
-           "config": {k: getattr(args, k) for k in ("n_layer", "n_head", "n_embd", "vocab",
-                                                    "batch", "seq", "bucket_mb", "mode",
-                                                    "allreduce", "zero", "comm_blocks",
-                                                    "emulate_comm", "emulate_world",
-                                                    "no_late_bucket",
-                                                    "no_split_optimizer",
-                                                    "main_stream_priority")}}
+           "config": {k: getattr(args, k) for k in config_keys}}
     if args.compare_overlap:
         alt = run(args, comm, overlap=args.no_overlap)
         out["other_overlap_setting"] = alt

@@ -22,11 +22,14 @@ struct AdamArgs {
   float bc1, bc2;     // 1 - beta^t
   float grad_scale;
   const int* step_dev;   // optional: step count read on the device (HIP-graph replayable)
+  const float* coef_dev; // CLIP kernels only: gradient-clip coefficient read on the device
 };
 
 // (Round 5's non-temporal fp32-state variant and the row-filtered form for an early update of a
 // tied table's untouched rows were measured no faster and removed in round 6.)
-template <int GDT>
+// CLIP: the gradient is also scaled by *coef_dev (csrc/grad_clip.hip), as a second fp32 multiply
+// after grad_scale: a coefficient of exactly 1.0 gives the bits of the CLIP = false kernel.
+template <int GDT, bool CLIP = false>
 __global__ void __launch_bounds__(256) adamw_kernel(AdamArgs a) {
   const int64_t nvec = a.n / 8;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
@@ -38,8 +41,11 @@ __global__ void __launch_bounds__(256) adamw_kernel(AdamArgs a) {
   }
   const float step = a.lr / bc1;
   const float inv_bc2 = 1.0f / bc2;
+  float coef = 1.f;
+  if constexpr (CLIP) coef = *a.coef_dev;
   auto body = [&](float& p, float& m, float& v, float g) {
     g *= a.grad_scale;
+    if constexpr (CLIP) g *= coef;
     m = a.beta1 * m + (1.f - a.beta1) * g;
     v = a.beta2 * v + (1.f - a.beta2) * g * g;
     const float denom = sqrtf(v * inv_bc2) + a.eps;
@@ -77,6 +83,16 @@ using namespace dlbb;
 
 static int launch_adamw(const AdamArgs& a, int grad_dtype, hipStream_t stream) {
   const int grid = stream_grid((a.n + 7) / 8, 256);
+  if (a.coef_dev) {
+    if (grad_dtype == DT_BF16) {
+      hipLaunchKernelGGL((adamw_kernel<DT_BF16, true>), dim3(grid), dim3(256), 0, stream, a);
+    } else if (grad_dtype == DT_F32) {
+      hipLaunchKernelGGL((adamw_kernel<DT_F32, true>), dim3(grid), dim3(256), 0, stream, a);
+    } else {
+      return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   if (grad_dtype == DT_BF16) {
     hipLaunchKernelGGL((adamw_kernel<DT_BF16>), dim3(grid), dim3(256), 0, stream, a);
   } else if (grad_dtype == DT_F32) {
@@ -94,7 +110,7 @@ DLBB_API int dlbb_adamw(float* p, float* m, float* v, const void* g, int grad_dt
   if (step < 1) return hipErrorInvalidValue;
   AdamArgs a{p, m, v, g, static_cast<uint16_t*>(p_bf16), n, lr, beta1, beta2, eps,
              weight_decay, 1.f - powf(beta1, static_cast<float>(step)),
-             1.f - powf(beta2, static_cast<float>(step)), grad_scale, nullptr};
+             1.f - powf(beta2, static_cast<float>(step)), grad_scale, nullptr, nullptr};
   return launch_adamw(a, grad_dtype, stream);
 }
 
@@ -107,6 +123,32 @@ DLBB_API int dlbb_adamw_devstep(float* p, float* m, float* v, const void* g, int
   if (n <= 0) return hipSuccess;
   if (!step_dev) return hipErrorInvalidValue;
   AdamArgs a{p, m, v, g, static_cast<uint16_t*>(p_bf16), n, lr, beta1, beta2, eps,
-             weight_decay, 1.f, 1.f, grad_scale, step_dev};
+             weight_decay, 1.f, 1.f, grad_scale, step_dev, nullptr};
+  return launch_adamw(a, grad_dtype, stream);
+}
+
+// The two forms above with the gradient also scaled by the clip coefficient `coef_dev[0]` read on
+// the device (g *= grad_scale; g *= *coef_dev): no host sync between the norm and the update.
+DLBB_API int dlbb_adamw_clip(float* p, float* m, float* v, const void* g, int grad_dtype,
+                             void* p_bf16, int64_t n, float lr, float beta1, float beta2,
+                             float eps, float weight_decay, int step, float grad_scale,
+                             const float* coef_dev, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (step < 1 || !coef_dev) return hipErrorInvalidValue;
+  AdamArgs a{p, m, v, g, static_cast<uint16_t*>(p_bf16), n, lr, beta1, beta2, eps,
+             weight_decay, 1.f - powf(beta1, static_cast<float>(step)),
+             1.f - powf(beta2, static_cast<float>(step)), grad_scale, nullptr, coef_dev};
+  return launch_adamw(a, grad_dtype, stream);
+}
+
+DLBB_API int dlbb_adamw_devstep_clip(float* p, float* m, float* v, const void* g, int grad_dtype,
+                                     void* p_bf16, int64_t n, float lr, float beta1,
+                                     float beta2, float eps, float weight_decay,
+                                     const int* step_dev, float grad_scale,
+                                     const float* coef_dev, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (!step_dev || !coef_dev) return hipErrorInvalidValue;
+  AdamArgs a{p, m, v, g, static_cast<uint16_t*>(p_bf16), n, lr, beta1, beta2, eps,
+             weight_decay, 1.f, 1.f, grad_scale, step_dev, coef_dev};
   return launch_adamw(a, grad_dtype, stream);
 }

@@ -9,6 +9,7 @@
   MXFP4 (W4A16) skinny GEMM of the opt-in MXFP4-weight decode step.
 * :mod:`.norm_act` — fused residual+LayerNorm and bias+GELU (fwd + bwd, autograd).
 * :mod:`.optim` — flat fused AdamW.
+* :mod:`.clip` — global gradient-norm clipping: bucket sum-of-squares, device-side coefficient.
 * :mod:`.xent` — fused softmax cross-entropy on bf16 logits; LM-head-fused linear + loss.
 * :mod:`.decode` — KV cache (bf16, or opt-in e4m3 codes with one fp32 scale per row), append, and
   single-query (decode) attention split over the keys.
@@ -25,6 +26,7 @@ from .mxfp4 import (quantize_mxfp4, dequantize_mxfp4, quantize_weight_mxfp4, lin
                     w4_linear, w4_contract_error, w4_skinny_plan, W4_LAUNCHES)
 from .norm_act import layernorm, bias_gelu
 from .optim import FlatAdamW
+from .clip import GradClipper, grad_sumsq, clip_coef, sumsq_plan
 from .xent import cross_entropy, linear_cross_entropy
 from .attention import causal_attention
 from .decode import KVCache, kv_append, decode_attention, CHUNK, CHUNK_FP8
@@ -35,4 +37,5 @@ __all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "CHUNK_FP8", "ca
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
            "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES",
            "quantize_mxfp4", "dequantize_mxfp4", "quantize_weight_mxfp4", "linear_w4",
-           "w4_linear", "w4_contract_error", "w4_skinny_plan", "W4_LAUNCHES"]
+           "w4_linear", "w4_contract_error", "w4_skinny_plan", "W4_LAUNCHES", "GradClipper",
+           "grad_sumsq", "clip_coef", "sumsq_plan"]

@@ -119,6 +119,17 @@ _SIGS = {
     "dlbb_adamw_devstep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                    c_int64, c_float, c_float, c_float, c_float, c_float,
                                    c_void_p, c_float, c_void_p]),
+    "dlbb_adamw_clip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                c_float, c_float, c_float, c_float, c_float, c_int, c_float,
+                                c_void_p, c_void_p]),
+    "dlbb_adamw_devstep_clip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_int64, c_float, c_float, c_float, c_float, c_float,
+                                        c_void_p, c_float, c_void_p, c_void_p]),
+    "dlbb_grad_sumsq": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p]),
+    "dlbb_grad_sumsq_tune": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int,
+                                     c_void_p]),
+    "dlbb_grad_sumsq_plan": (c_int, [c_int64, ctypes.POINTER(c_int)]),
+    "dlbb_clip_coef": (c_int, [c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p]),
     "dlbb_xent_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                               c_void_p]),
     "dlbb_xent_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import check, dt, use_hip
+from .clip import check_coef
 
 
 class FlatAdamW:
@@ -37,12 +38,16 @@ class FlatAdamW:
 
     @torch.no_grad()
     def step(self, grad: torch.Tensor, working_bf16: Optional[torch.Tensor] = None,
-             grad_scale: float = 1.0, ranges=None, advance: bool = True) -> None:
+             grad_scale: float = 1.0, ranges=None, advance: bool = True,
+             coef_dev: Optional[torch.Tensor] = None) -> None:
         """One AdamW update. ``ranges``: update only these [start, end) element ranges (one
         kernel each; the rest of the step's ranges follow in later calls with
-        ``advance=False``, so the step count — and the bias correction — moves once)."""
+        ``advance=False``, so the step count — and the bias correction — moves once).
+        ``coef_dev``: one fp32 element in device memory (``ops.clip.GradClipper.finish``) that
+        scales the gradient after ``grad_scale`` — read by the kernel, never by the host."""
         if grad.numel() != self.p.numel():
             raise ValueError("grad / master size mismatch")
+        check_coef(coef_dev, self.p)
         if advance:
             self.t += 1
             if self.t_dev is not None and use_hip(self.p, grad):
@@ -56,7 +61,20 @@ class FlatAdamW:
                 continue
             p, m, v, g = self.p[a:e], self.m[a:e], self.v[a:e], grad[a:e]
             w = working_bf16[a:e] if working_bf16 is not None else None
-            if use_hip(self.p, grad) and self.t_dev is not None:
+            if coef_dev is not None and use_hip(self.p, grad):
+                if self.t_dev is not None:
+                    check(_lib.lib().dlbb_adamw_devstep_clip(
+                        p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), dt(grad),
+                        _lib.ptr(w), e - a, self.lr, b1, b2, self.eps, self.wd,
+                        self.t_dev.data_ptr(), float(grad_scale), coef_dev.data_ptr(),
+                        _lib.stream(self.p.device)), "adamw_devstep_clip")
+                else:
+                    check(_lib.lib().dlbb_adamw_clip(
+                        p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), dt(grad),
+                        _lib.ptr(w), e - a, self.lr, b1, b2, self.eps, self.wd, self.t,
+                        float(grad_scale), coef_dev.data_ptr(), _lib.stream(self.p.device)),
+                        "adamw_clip")
+            elif use_hip(self.p, grad) and self.t_dev is not None:
                 check(_lib.lib().dlbb_adamw_devstep(
                     p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), dt(grad),
                     _lib.ptr(w), e - a, self.lr, b1, b2, self.eps, self.wd,
@@ -69,6 +87,8 @@ class FlatAdamW:
                     float(grad_scale), _lib.stream(self.p.device)), "adamw")
             else:
                 gf = g.float() * grad_scale
+                if coef_dev is not None:
+                    gf = gf * coef_dev.reshape(())
                 m.mul_(b1).add_(gf, alpha=1 - b1)
                 v.mul_(b2).addcmul_(gf, gf, value=1 - b2)
                 bc1 = 1 - b1 ** self.t

@@ -26,6 +26,16 @@ the MI355X-native replacement used by the GPT-2 DDP microbenchmark:
   priority its workgroups took CU slots ahead of the backward's hipBLASLt Stream-K GEMMs, whose
   persistent grids then stalled (+69 % step time in 4 of 15 settings;
   profiles/r02_overlap/SUMMARY.md). ``comm_blocks`` is the reductions' CU budget.
+* **Gradient clipping** (``clip_grad_norm=F``, off by default): the global L2 norm of the averaged
+  gradient is clipped at ``F`` as ``torch.nn.utils.clip_grad_norm_`` does, entirely on the device
+  (``ops/clip.py``): each reduced bucket's sum of squares is taken where its AdamW range would
+  have run (same stream, same ordering), one small kernel forms the norm and the coefficient
+  after backward, and every AdamW range reads that coefficient from device memory — no host
+  sync, no pass rewriting the gradients, and the step still captures as a HIP graph. The AdamW
+  of the head buckets therefore moves after backward (it needs the global norm). Replicated
+  DDP already relies on every rank holding bit-identical reduced gradients (AdamW is replicated);
+  the norm rests on the same assumption and nothing is added to enforce it. The norm also relies
+  on the alignment padding inside ``flat_grad`` being zero (see ``zero_grad``).
 """
 
 from __future__ import annotations
@@ -37,7 +47,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from ..ops import FlatAdamW
+from ..ops import FlatAdamW, GradClipper
 from ..ops.elementwise import ChunkTable, ScaleTable, reduce_sum, spin_ns
 from ..ops.xent import mark_unit_upstream
 from ..utils import tracing
@@ -86,7 +96,7 @@ class FlatParamTrainer:
                  overlap: bool = True, mode: str = "view", allreduce: str = "rccl",
                  grad_dtype: torch.dtype = torch.bfloat16, comm_blocks: Optional[int] = None,
                  emulate_comm=False, emulate_world: int = 8, split_optimizer: bool = True,
-                 late_bucket: bool = True):
+                 late_bucket: bool = True, clip_grad_norm: Optional[float] = None):
         if mode == "view" and grad_dtype != torch.bfloat16:
             raise ValueError("grad_dtype must be the parameter dtype (bf16) in mode='view': "
                              "autograd accumulates straight into the bucket views; use "
@@ -143,6 +153,13 @@ class FlatParamTrainer:
         for st, en, ps in spans:
             self._add_bucket(st, en, ps)
         self._init_optimizer(lr, betas, weight_decay)
+        # global gradient-norm clipping (None = off: no clipper, today's launches). One
+        # sum-of-squares range per bucket where the optimizer runs per bucket range, else one
+        # range over the whole reduced gradient. ``grad_norm``: device fp32 scalar, the last
+        # step's global norm of the averaged gradient before clipping.
+        self.clip_grad_norm = clip_grad_norm
+        self._clipper: Optional[GradClipper] = None
+        self.grad_norm: Optional[torch.Tensor] = None
         self._offsets = {id(p): o for p, o in zip(order, offs)}
         self._params = order
         # weight-gradient GEMMs of sink params run on this side stream (off the backward's
@@ -220,6 +237,10 @@ class FlatParamTrainer:
         # buckets are reduced, then the last bucket — whose all-reduce (it is ready only at the
         # end of backward) overlaps the first range's AdamW instead of preceding all of it
         self.split_optimizer = split_optimizer
+        if clip_grad_norm is not None:
+            self._clipper = GradClipper(len(self.buckets) if self._clip_per_bucket() else 1,
+                                        clip_grad_norm, dev)
+            self.grad_norm = self._clipper.norm
         self.opt_overlap = ((int(_OPT_OVERLAP) if _OPT_OVERLAP is not None
                              else (2 if self.world == 1 else 0))
                             if dev.type == "cuda" else 0)
@@ -294,9 +315,23 @@ class FlatParamTrainer:
         self.master = self.flat_param.float()
         self.opt = FlatAdamW(self.master, lr=lr, betas=betas, weight_decay=weight_decay)
 
-    def _optimizer_step(self, ranges=None, advance: bool = True) -> None:
+    def _optimizer_step(self, ranges=None, advance: bool = True, coef_dev=None) -> None:
         self.opt.step(self.flat_grad, working_bf16=self.flat_param, grad_scale=1.0 / self.world,
-                      ranges=ranges, advance=advance)
+                      ranges=ranges, advance=advance, coef_dev=coef_dev)
+
+    def _clip_coef_full(self) -> torch.Tensor:
+        """Clipping without per-bucket ranges: one sum of squares over the whole reduced
+        gradient (after ``finish``), then norm and coefficient."""
+        self._clipper.accumulate(0, self.flat_grad)
+        return self._clipper.finish(1.0 / self.world)
+
+    def last_grad_norm(self) -> float:
+        """Global L2 norm of the last step's averaged gradient, before clipping, as a host float
+        (synchronises; the step itself never does for clipping)."""
+        if self.grad_norm is None:
+            raise RuntimeError("gradient clipping is off (clip_grad_norm=None): no norm is "
+                               "computed")
+        return float(self.grad_norm.item())
 
     # ------------------------------------------------------------------ buckets
     def _add_bucket(self, start: int, end: int, params) -> None:
@@ -312,6 +347,8 @@ class FlatParamTrainer:
         self._opt_issued = 0
         for b in self.buckets:
             b.opt_done = False
+        if self._clipper is not None:
+            self._clipper.reset()
         self._seen.clear()
         for p in self._params:          # per-step use counters of multi-use gradient sinks
             if getattr(p, "_dlbb_sink_count", 0):
@@ -342,7 +379,9 @@ class FlatParamTrainer:
         after everything that produced or reads the bucket — the main stream up to now (its
         dgrads read these weights before the sinks report them ready, ops/linear_fn.py), the
         weight-gradient side streams, and the bucket's all-reduce. The first range of the step
-        advances the AdamW step count; the tail bucket waits for this stream in ``step``."""
+        advances the AdamW step count; the tail bucket waits for this stream in ``step``.
+        With gradient clipping the bucket's sum of squares takes the AdamW range's place (the
+        update needs the global norm and runs after backward)."""
         if (not self.opt_overlap or not self._in_step or b.idx == len(self.buckets) - 1
                 or not self._split_optimizer_ok()):
             return
@@ -351,7 +390,10 @@ class FlatParamTrainer:
         self._wait_wgrad(os_)
         with torch.cuda.stream(os_):
             self._wait_bucket(b)
-            self._optimizer_step(ranges=[(b.start, b.end)], advance=self._opt_issued == 0)
+            if self._clipper is not None:
+                self._clipper.accumulate(b.idx, self.flat_grad[b.start:b.end])
+            else:
+                self._optimizer_step(ranges=[(b.start, b.end)], advance=self._opt_issued == 0)
         self._opt_issued += 1
         b.opt_done = True
 
@@ -547,6 +589,10 @@ class FlatParamTrainer:
 
     # ------------------------------------------------------------------ step
     def zero_grad(self) -> None:
+        # The alignment padding inside flat_grad (between params and at bucket ends) is zero
+        # and stays zero: allocated as zeros, and only the params' slices are ever written (grad
+        # views / sinks in mode "view", the chunk copies in mode "flatten"); reductions sum
+        # zeros. The clipping norm sums whole buckets and relies on it.
         if self.mode == "view":
             self.flat_grad.zero_()
             for p in self._params:      # sink writers may store instead of accumulate once
@@ -586,19 +632,34 @@ class FlatParamTrainer:
                     self._wait_bucket(b)
                 if self._wgrad_stream is not None:
                     self._wait_wgrad(cur)
-                adv = self._opt_issued == 0
-                if todo:
-                    self._optimizer_step(
-                        ranges=[(0, tail.start)] if len(todo) == len(head)
-                        else [(b.start, b.end) for b in todo], advance=adv)
-                    adv = False
-                self._wait_bucket(tail)
-                self._optimizer_step(ranges=[(tail.start, self.numel)], advance=adv)
+                if self._clipper is not None:
+                    # the buckets not summed during backward, the tail bucket, then the norm;
+                    # the AdamW ranges (head, tail) read the coefficient from device memory
+                    for b in todo:
+                        self._clipper.accumulate(b.idx, self.flat_grad[b.start:b.end])
+                    self._wait_bucket(tail)
+                    self._clipper.accumulate(tail.idx, self.flat_grad[tail.start:self.numel])
+                    coef = self._clipper.finish(1.0 / self.world)
+                    self._optimizer_step(ranges=[(0, tail.start)], advance=True, coef_dev=coef)
+                    self._optimizer_step(ranges=[(tail.start, self.numel)], advance=False,
+                                         coef_dev=coef)
+                else:
+                    adv = self._opt_issued == 0
+                    if todo:
+                        self._optimizer_step(
+                            ranges=[(0, tail.start)] if len(todo) == len(head)
+                            else [(b.start, b.end) for b in todo], advance=adv)
+                        adv = False
+                    self._wait_bucket(tail)
+                    self._optimizer_step(ranges=[(tail.start, self.numel)], advance=adv)
         else:
             with tracing.range("grad_sync_tail"):
                 self.finish()
             with tracing.range("optimizer"):
-                self._optimizer_step()
+                if self._clipper is not None:
+                    self._optimizer_step(coef_dev=self._clip_coef_full())
+                else:
+                    self._optimizer_step()
         self._in_step = False
         if self._tl is not None:
             self._tl["opt_end"] = torch.cuda.Event(enable_timing=True)
@@ -609,6 +670,10 @@ class FlatParamTrainer:
     def _split_optimizer_ok(self) -> bool:
         return (self.split_optimizer and len(self.buckets) > 1 and self.mode == "view"
                 and type(self)._optimizer_step is FlatParamTrainer._optimizer_step)
+
+    def _clip_per_bucket(self) -> bool:
+        """One clipping range per bucket exactly where the optimizer runs per bucket range."""
+        return self._split_optimizer_ok()
 
     def comm_tail_report(self) -> Optional[dict]:
         """For the last step run with ``timeline = True`` (stream-issued reductions: custom,

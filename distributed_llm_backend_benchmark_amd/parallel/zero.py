@@ -13,6 +13,8 @@ multiple of ``world x 64`` elements and split into ``world`` equal chunks; rank 
 * optimizer: ONE fused AdamW launch over the rank's fp32 master shard (1/world of the model:
   master + moments are sharded), 1/world averaging fused, writing a bf16 parameter shard;
 * **all-gather** of every bucket's bf16 chunks back into the flat parameter buffer.
+* optional gradient clipping (``clip_grad_norm=F``, see :mod:`.ddp`): the shards are disjoint, so
+  each rank sums the squares of its ``grad_shard`` and ONE float is all-reduced before the norm.
 
 Traffic per step equals DDP's all-reduce (reduce-scatter + all-gather = 2(P-1)/P · bytes) while
 optimizer memory drops by P.
@@ -79,10 +81,20 @@ class ShardedTrainer(FlatParamTrainer):
             b.work = dist.reduce_scatter_tensor(out, self.flat_grad[b.start:b.end],
                                                 async_op=True)
 
-    def _optimizer_step(self) -> None:
+    def _optimizer_step(self, coef_dev=None) -> None:
         self.opt.step(self.grad_shard, working_bf16=self.param_shard,
-                      grad_scale=1.0 / self.world)
+                      grad_scale=1.0 / self.world, coef_dev=coef_dev)
         self._gather_params()
+
+    def _clip_coef_full(self) -> torch.Tensor:
+        """Global norm from disjoint shards: this rank's sum of squares over ``grad_shard``, one
+        float all-reduced, then norm and coefficient (identical on every rank). The shard's
+        alignment padding is zero: it is copied / reduce-scattered from ``flat_grad``'s zero
+        padding, and the norm relies on that. World 1 skips the all-reduce as it skips the
+        other collectives."""
+        self._clipper.accumulate(0, self.grad_shard)
+        group = dist.group.WORLD if self.world > 1 else None
+        return self._clipper.finish(1.0 / self.world, group=group)
 
     def _replicated_state(self) -> bool:
         return False

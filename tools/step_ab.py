@@ -8,6 +8,9 @@ One JSON line per run.
   split_cap=N    weight-gradient split-K capped at N (ops/gemm.set_wgrad_split_cap)
   wgrad_fused    weight-gradient split-K combined in-launch (ops/gemm.set_wgrad_fused)
   no_wgrad_side  weight gradients on the compute stream (parallel/ddp._WGRAD_STREAM)
+  clip=F         gradient-norm clipping at F (--clip-grad-norm F; base = clipping off)
+  opt_overlap=N  per-bucket AdamW during backward: 0 after backward, 1 own stream, 2 on the
+                 weight-gradient stream (parallel/ddp._OPT_OVERLAP; world 1 defaults to 2)
 
 (Round 6 also ran a two-pass LayerNorm column reduce and the embedding token sort moved into the
 forward on a side stream through this tool — profiles/r06_step/step_ab_presort_colreduce.jsonl,
@@ -24,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 _DEFAULT_WGRAD_STREAM = [None]
+_DEFAULT_OPT_OVERLAP = [None]
 
 
 def apply(name):
@@ -33,6 +37,9 @@ def apply(name):
     gemm.set_wgrad_split_cap(None)
     gemm.set_wgrad_fused(False)
     ddp._WGRAD_STREAM = _DEFAULT_WGRAD_STREAM[0]
+    ddp._OPT_OVERLAP = _DEFAULT_OPT_OVERLAP[0]
+    if name.startswith("opt_overlap="):
+        ddp._OPT_OVERLAP = name.split("=")[1]
     if name == "wgrad_fused":
         gemm.set_wgrad_fused(True)
     if name == "no_wgrad_side":
@@ -56,14 +63,20 @@ def main():
     from distributed_llm_backend_benchmark_amd.parallel import ddp
 
     _DEFAULT_WGRAD_STREAM[0] = ddp._WGRAD_STREAM
+    _DEFAULT_OPT_OVERLAP[0] = ddp._OPT_OVERLAP
     comm = init_distributed("auto")
     args = train_ddp.parse_args(["--steps", str(a.steps), "--warmup", str(a.warmup)])
     for rep in range(a.reps):
         for name in a.variants.split(","):
             apply(name)
+            args.clip_grad_norm = float(name.split("=")[1]) if name.startswith("clip=") else None
             res = train_ddp.run(args, comm, overlap=True)
-            print(json.dumps({"rep": rep, "variant": name, "ms_per_step": res["ms_per_step"],
-                              "side_stream_checks": res["side_stream_checks"]}), flush=True)
+            rec = {"rep": rep, "variant": name, "ms_per_step": res["ms_per_step"],
+                   "side_stream_checks": res["side_stream_checks"]}
+            if args.clip_grad_norm is not None:
+                rec["grad_norm_first_step"] = res["grad_norm_first_step"]
+                rec["grad_norm_last"] = res["grad_norm_last"]
+            print(json.dumps(rec), flush=True)
     apply("base")
     comm.destroy()
     return 0
