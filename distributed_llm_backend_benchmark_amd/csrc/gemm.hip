@@ -2060,11 +2060,83 @@ __global__ void __launch_bounds__(kThreads2, 1) gemm_bf16_nt_192_pp_spread_bal(G
 
 using namespace dlbb;
 
+// Host-side record of the __global__ the C entry points below launched last (tests assert the
+// kernel a case is named for ran, not one of the dispatchers' silent fallbacks). One id per
+// kernel; the persistent forms are kGk..PERSIST + their LEAN kind, a stamped ping-pong twin is
+// its kernel's id + kGkStamped. Set by every launch site, read by dlbb_gemm_last_kernel().
+enum GemmKernelId : int {
+  GK_NONE = 0,
+  GK_NT_128 = 1,
+  GK_NT_256_DEEP = 2,
+  GK_NT_256_PP = 3,
+  GK_NT_256_PP_BAL = 4,
+  GK_NT_192_PP = 5,
+  GK_NT_192_PP_BAL = 6,
+  GK_NT_192_SPREAD = 7,
+  GK_NT_192_SPREAD_BAL = 8,
+  GK_NT_256_STREAMK = 9,
+  GK_NT_256_STREAMK_BAL = 10,
+  GK_NN_256_PP = 11,
+  GK_NN_256_PP_BAL = 12,
+  GK_TN_256_PP = 13,
+  GK_TN_256_PP_BAL = 14,
+  GK_NT_256_PERSIST = 16,        // + PP_PLAIN .. PP_BIAS_GELU_ERF
+  GK_NT_256_PERSIST_BAL = 24,    // + PP_PLAIN .. PP_BIAS_GELU_ERF
+  GK_NN_256_PERSIST_BAL = 32,    // + PP_PLAIN, PP_DGELU_TANH, PP_DGELU_ERF
+  kGkStamped = 64,
+};
+static int dlbb_gemm_last = GK_NONE;
+
+DLBB_API int dlbb_gemm_last_kernel() { return dlbb_gemm_last; }
+
+DLBB_API const char* dlbb_gemm_kernel_name(int id) {
+  switch (id) {
+    case GK_NONE: return "none";
+    case GK_NT_128: return "gemm_bf16_nt_kernel";
+    case GK_NT_256_DEEP: return "gemm_bf16_nt_256_deep";
+    case GK_NT_256_PP: return "gemm_bf16_nt_256_pingpong3";
+    case GK_NT_256_PP_BAL: return "gemm_bf16_nt_256_pingpong3_bal";
+    case GK_NT_192_PP: return "gemm_bf16_nt_192_pingpong3";
+    case GK_NT_192_PP_BAL: return "gemm_bf16_nt_192_pingpong3_bal";
+    case GK_NT_192_SPREAD: return "gemm_bf16_nt_192_pp_spread";
+    case GK_NT_192_SPREAD_BAL: return "gemm_bf16_nt_192_pp_spread_bal";
+    case GK_NT_256_STREAMK: return "gemm_bf16_nt_256_streamk";
+    case GK_NT_256_STREAMK_BAL: return "gemm_bf16_nt_256_streamk_bal";
+    case GK_NN_256_PP: return "gemm_bf16_nn_256_pingpong3";
+    case GK_NN_256_PP_BAL: return "gemm_bf16_nn_256_pingpong3_bal";
+    case GK_TN_256_PP: return "gemm_bf16_tn_256_pingpong3";
+    case GK_TN_256_PP_BAL: return "gemm_bf16_tn_256_pingpong3_bal";
+    case GK_NT_256_PERSIST + PP_PLAIN: return "gemm_bf16_nt_256_pp_persist<plain>";
+    case GK_NT_256_PERSIST + PP_BIAS: return "gemm_bf16_nt_256_pp_persist<bias>";
+    case GK_NT_256_PERSIST + PP_BIAS_GELU_TANH: return "gemm_bf16_nt_256_pp_persist<bias_gelu_tanh>";
+    case GK_NT_256_PERSIST + PP_BIAS_GELU_ERF: return "gemm_bf16_nt_256_pp_persist<bias_gelu_erf>";
+    case GK_NT_256_PERSIST_BAL + PP_PLAIN: return "gemm_bf16_nt_256_pp_persist_bal<plain>";
+    case GK_NT_256_PERSIST_BAL + PP_BIAS: return "gemm_bf16_nt_256_pp_persist_bal<bias>";
+    case GK_NT_256_PERSIST_BAL + PP_BIAS_GELU_TANH:
+      return "gemm_bf16_nt_256_pp_persist_bal<bias_gelu_tanh>";
+    case GK_NT_256_PERSIST_BAL + PP_BIAS_GELU_ERF:
+      return "gemm_bf16_nt_256_pp_persist_bal<bias_gelu_erf>";
+    case GK_NN_256_PERSIST_BAL + PP_PLAIN: return "gemm_bf16_nn_256_pp_persist_bal<plain>";
+    case GK_NN_256_PERSIST_BAL + PP_DGELU_TANH:
+      return "gemm_bf16_nn_256_pp_persist_bal<dgelu_tanh>";
+    case GK_NN_256_PERSIST_BAL + PP_DGELU_ERF:
+      return "gemm_bf16_nn_256_pp_persist_bal<dgelu_erf>";
+    case kGkStamped + GK_NT_256_PP: return "gemm_bf16_nt_256_pingpong3_st";
+    case kGkStamped + GK_NT_256_PP_BAL: return "gemm_bf16_nt_256_pingpong3_bal_st";
+    case kGkStamped + GK_NN_256_PP: return "gemm_bf16_nn_256_pingpong3_st";
+    case kGkStamped + GK_NN_256_PP_BAL: return "gemm_bf16_nn_256_pingpong3_bal_st";
+    case kGkStamped + GK_TN_256_PP: return "gemm_bf16_tn_256_pingpong3_st";
+    case kGkStamped + GK_TN_256_PP_BAL: return "gemm_bf16_tn_256_pingpong3_bal_st";
+    default: return "unknown";
+  }
+}
+
 // Launch a ping-pong kernel, or its stamped twin when stamping is on (dlbb_stamps_set).
-#define DLBB_PP_LAUNCH(KERNEL, KIND, GRID, ARGS)                                          \
+#define DLBB_PP_LAUNCH(KERNEL, ID, KIND, GRID, ARGS)                                      \
   do {                                                                                   \
     const dim3 g_(GRID);                                                                 \
     uint64_t* st_ = stamp_acquire(KIND, static_cast<int64_t>(g_.x) * g_.y);              \
+    dlbb_gemm_last = st_ ? kGkStamped + (ID) : (ID);                                     \
     if (st_)                                                                             \
       hipLaunchKernelGGL(KERNEL##_st, g_, dim3(kThreads2), kPP6Lds, stream, ARGS, st_);  \
     else                                                                                 \
@@ -2181,7 +2253,9 @@ DLBB_API int dlbb_gemm_bf16_nt_streamk(const void* A, int64_t lda, const void* B
              vec_ok, 0};
   SkArgs s{static_cast<float*>(ws), cnt, static_cast<int>(plan[1]), static_cast<int>(K / BK)};
   const dim3 g(static_cast<unsigned>(plan[0])), b(kThreads2);
-  if (use_bal(plan[1], false))
+  const bool bal = use_bal(plan[1], false);
+  dlbb_gemm_last = bal ? GK_NT_256_STREAMK_BAL : GK_NT_256_STREAMK;
+  if (bal)
     hipLaunchKernelGGL(gemm_bf16_nt_256_streamk_bal, g, b, kPP6Lds, stream, a, s);
   else
     hipLaunchKernelGGL(gemm_bf16_nt_256_streamk, g, b, kPP6Lds, stream, a, s);
@@ -2255,6 +2329,7 @@ DLBB_API int dlbb_gemm_bf16_nt_v(const void* A, int64_t lda, const void* B, int6
     const int64_t grid = tiles < num_cus() ? tiles : num_cus();
     const dim3 g(static_cast<unsigned>(grid)), b(kThreads2);
     const bool bal = use_bal(K / BK, false);
+    dlbb_gemm_last = bal ? GK_NT_192_SPREAD_BAL : GK_NT_192_SPREAD;
     if (bal) hipLaunchKernelGGL(gemm_bf16_nt_192_pp_spread_bal<12>, g, b, kPP192Lds, stream, a);
     else hipLaunchKernelGGL(gemm_bf16_nt_192_pp_spread<12>, g, b, kPP192Lds, stream, a);
     return hipGetLastError();
@@ -2263,7 +2338,9 @@ DLBB_API int dlbb_gemm_bf16_nt_v(const void* A, int64_t lda, const void* B, int6
   if (variant == 1 && N % 192 == 0 && M % 8 == 0 && M >= 8 &&
       lda * 2 * 256 + K * 2 < (1LL << 31) && ldb * 2 * 192 + K * 2 < (1LL << 31)) {
     const dim3 g(static_cast<unsigned>(((M + BM2 - 1) / BM2) * (N / 192))), b(kThreads2);
-    if (use_bal(K / BK, false))
+    const bool bal = use_bal(K / BK, false);
+    dlbb_gemm_last = bal ? GK_NT_192_PP_BAL : GK_NT_192_PP;
+    if (bal)
       hipLaunchKernelGGL(gemm_bf16_nt_192_pingpong3_bal, g, b, kPP192Lds, stream, a);
     else
       hipLaunchKernelGGL(gemm_bf16_nt_192_pingpong3, g, b, kPP192Lds, stream, a);
@@ -2306,6 +2383,7 @@ DLBB_API int dlbb_gemm_bf16_nt_v(const void* A, int64_t lda, const void* B, int6
       const bool bal = use_bal(K / BK, false);
 #define DLBB_PP_PERSIST_LAUNCH(L)                                                          \
   do {                                                                                     \
+    dlbb_gemm_last = (bal ? GK_NT_256_PERSIST_BAL : GK_NT_256_PERSIST) + (L);              \
     if (bal) hipLaunchKernelGGL(gemm_bf16_nt_256_pp_persist_bal<L>, gp, bp, kPP6Lds, stream, a); \
     else hipLaunchKernelGGL(gemm_bf16_nt_256_pp_persist<L>, gp, bp, kPP6Lds, stream, a);   \
   } while (0)
@@ -2318,15 +2396,18 @@ DLBB_API int dlbb_gemm_bf16_nt_v(const void* A, int64_t lda, const void* B, int6
 #undef DLBB_PP_PERSIST_LAUNCH
       return hipGetLastError();
     }
-    if (mode == 6 && use_bal(K / BK, false))
-      DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3_bal, STAMP_GEMM_NT, g, a);
-    else if (mode == 6)
-      DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3, STAMP_GEMM_NT, g, a);
-    else
+    if (mode == 6 && use_bal(K / BK, false)) {
+      DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3_bal, GK_NT_256_PP_BAL, STAMP_GEMM_NT, g, a);
+    } else if (mode == 6) {
+      DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3, GK_NT_256_PP, STAMP_GEMM_NT, g, a);
+    } else {
+      dlbb_gemm_last = GK_NT_256_DEEP;
       hipLaunchKernelGGL(gemm_bf16_nt_256_deep, g, b, 2 * kBuf2Bytes, stream, a);
+    }
     return hipGetLastError();
   }
   const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+  dlbb_gemm_last = GK_NT_128;
   hipLaunchKernelGGL(gemm_bf16_nt_kernel, dim3(static_cast<unsigned>(tiles)), dim3(kThreads),
                      4 * kTileBytes, stream, a);
   return hipGetLastError();
@@ -2372,10 +2453,10 @@ DLBB_API int dlbb_gemm_bf16_nn(const void* A, int64_t lda, const void* B, int64_
     a.out_f32 = 1;
     a.vec_ok = (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && N % 8 == 0;
     if (use_bal(a.kt_split, true))
-      DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3_bal, STAMP_GEMM_NN,
+      DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3_bal, GK_NN_256_PP_BAL, STAMP_GEMM_NN,
                      dim3(static_cast<unsigned>(tiles256), split), a);
     else
-      DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3, STAMP_GEMM_NN,
+      DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3, GK_NN_256_PP, STAMP_GEMM_NN,
                      dim3(static_cast<unsigned>(tiles256), split), a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -2390,6 +2471,7 @@ DLBB_API int dlbb_gemm_bf16_nn(const void* A, int64_t lda, const void* B, int64_
                      : epi == EPI_DGELU_TANH ? PP_DGELU_TANH
                      : epi == EPI_DGELU_ERF ? PP_DGELU_ERF : -1;
     const dim3 gp(static_cast<unsigned>(num_cus())), bp(kThreads2);
+    if (lean >= 0) dlbb_gemm_last = GK_NN_256_PERSIST_BAL + lean;
     switch (lean) {
       case PP_PLAIN:
         hipLaunchKernelGGL(gemm_bf16_nn_256_pp_persist_bal<PP_PLAIN>, gp, bp, kPP6Lds, stream, a);
@@ -2407,10 +2489,10 @@ DLBB_API int dlbb_gemm_bf16_nn(const void* A, int64_t lda, const void* B, int64_
     }
   }
   if (use_bal(nkt, true))
-    DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3_bal, STAMP_GEMM_NN,
+    DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3_bal, GK_NN_256_PP_BAL, STAMP_GEMM_NN,
                    dim3(static_cast<unsigned>(tiles256)), a);
   else
-    DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3, STAMP_GEMM_NN,
+    DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3, GK_NN_256_PP, STAMP_GEMM_NN,
                    dim3(static_cast<unsigned>(tiles256)), a);
   return hipGetLastError();
 }
@@ -2447,11 +2529,12 @@ DLBB_API int dlbb_gemm_bf16_nt_split(const void* A, int64_t lda, const void* B, 
   const dim3 g(static_cast<unsigned>(tiles), static_cast<unsigned>(split)), b(kThreads2);
   const bool bal = use_bal(a.kt_split, false);
   if (tile192) {
+    dlbb_gemm_last = bal ? GK_NT_192_PP_BAL : GK_NT_192_PP;
     if (bal) hipLaunchKernelGGL(gemm_bf16_nt_192_pingpong3_bal, g, b, kPP192Lds, stream, a);
     else hipLaunchKernelGGL(gemm_bf16_nt_192_pingpong3, g, b, kPP192Lds, stream, a);
   } else {
-    if (bal) DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3_bal, STAMP_GEMM_NT, g, a);
-    else DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3, STAMP_GEMM_NT, g, a);
+    if (bal) DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3_bal, GK_NT_256_PP_BAL, STAMP_GEMM_NT, g, a);
+    else DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3, GK_NT_256_PP, STAMP_GEMM_NT, g, a);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -2495,18 +2578,18 @@ DLBB_API int dlbb_gemm_bf16_tn(const void* A, int64_t lda, const void* B, int64_
     a.vec_ok = N % 8 == 0;
     const dim3 g(static_cast<unsigned>(tiles256), static_cast<unsigned>(split));
     if (use_bal(a.kt_split, true))
-      DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3_bal, STAMP_GEMM_TN, g, a);
+      DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3_bal, GK_TN_256_PP_BAL, STAMP_GEMM_TN, g, a);
     else
-      DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3, STAMP_GEMM_TN, g, a);
+      DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3, GK_TN_256_PP, STAMP_GEMM_TN, g, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return dlbb_split_reduce_launch(ws, C, dt_f32, M * N, split, stream);
   }
   if (use_bal(nkt, true))
-    DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3_bal, STAMP_GEMM_TN,
+    DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3_bal, GK_TN_256_PP_BAL, STAMP_GEMM_TN,
                    dim3(static_cast<unsigned>(tiles256)), a);
   else
-    DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3, STAMP_GEMM_TN,
+    DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3, GK_TN_256_PP, STAMP_GEMM_TN,
                    dim3(static_cast<unsigned>(tiles256)), a);
   return hipGetLastError();
 }

@@ -98,6 +98,8 @@ _SIGS = {
                                  c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                  c_void_p, c_int64, c_int, c_int, c_void_p]),
     "dlbb_gemm_fp8_set_bal": (None, [c_int]),
+    "dlbb_gemm_last_kernel": (c_int, []),
+    "dlbb_gemm_kernel_name": (ctypes.c_char_p, [c_int]),
     "dlbb_gemm_set_tile": (None, [c_int]),
     "dlbb_gemm_set_stagger": (None, [c_int]),
     "dlbb_gemm_get_stagger": (c_int, []),
