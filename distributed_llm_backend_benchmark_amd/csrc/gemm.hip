@@ -63,8 +63,8 @@ struct GemmArgs {
   int epi;
   int out_f32;
   int vec_ok;              // 16-B aligned C / residual / preact / bias rows (vector epilogue)
-  int kt_split;            // NN split-K (gridDim.y > 1): K-tiles per split; split s writes fp32
-                           // partials to C + s * M * ldc
+  int kt_split;            // split-K of the NN, NT and TN ping-pong (gridDim.y > 1): K-tiles per
+                           // split; split s writes fp32 partials to C + s * M * ldc
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -1100,7 +1100,7 @@ __global__ void __launch_bounds__(kThreads2, 1) gemm_bf16_nt_256_pingpong3(GemmA
   pingpong_body<false>(a, smem);
 }
 
-// A/B variant (set_stagger(7)): the balanced DMA issue (BAL above).
+// The balanced DMA issue (BAL above); chosen per launch by dlbb_gemm_set_bal.
 __global__ void __launch_bounds__(kThreads2, 1) gemm_bf16_nt_256_pingpong3_bal(GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   pingpong_body<false, true>(a, smem);
@@ -2060,10 +2060,12 @@ __global__ void __launch_bounds__(kThreads2, 1) gemm_bf16_nt_192_pp_spread_bal(G
 
 using namespace dlbb;
 
-// Host-side record of the __global__ the C entry points below launched last (tests assert the
-// kernel a case is named for ran, not one of the dispatchers' silent fallbacks). One id per
-// kernel; the persistent forms are kGk..PERSIST + their LEAN kind, a stamped ping-pong twin is
-// its kernel's id + kGkStamped. Set by every launch site, read by dlbb_gemm_last_kernel().
+// Every __global__ the C entry points below launch, in ONE table indexed by its id. The id is what
+// dlbb_gemm_last_kernel() reports after a launch (tests assert the kernel a case is named for ran,
+// not one of the dispatchers' silent fallbacks) and the name what dlbb_gemm_kernel_name() gives it;
+// both are an interface (tests and profile tools read them). The ids are laid out so that a choice
+// is an index (pick): a kernel's balanced-DMA twin is id + 1 (of the NT persistent forms: + 8), a
+// persistent form is its family's id + the LEAN kind, a stamped twin reports id + kGkStamped.
 enum GemmKernelId : int {
   GK_NONE = 0,
   GK_NT_128 = 1,
@@ -2085,63 +2087,97 @@ enum GemmKernelId : int {
   GK_NN_256_PERSIST_BAL = 32,    // + PP_PLAIN, PP_DGELU_TANH, PP_DGELU_ERF
   kGkStamped = 64,
 };
+
+struct GemmKernel {
+  int id;
+  const char* name;
+  const void* fn;        // __global__(GemmArgs); Stream-K: (GemmArgs, SkArgs)
+  int lds, threads;      // dynamic LDS bytes, block size
+  const void* fn_st;     // stamped diagnostic twin __global__(GemmArgs, uint64_t*), if any
+  const char* name_st;
+};
+
+#define DLBB_FN(F) reinterpret_cast<const void*>(&F)
+#define DLBB_ROW(ID, F, LDS, THREADS) {ID, #F, DLBB_FN(F), LDS, THREADS}
+#define DLBB_PP_ROW(ID, F) {ID, #F, DLBB_FN(F), kPP6Lds, kThreads2, DLBB_FN(F##_st), #F "_st"}
+#define DLBB_LEAN_ROW(ID, F, KIND, TAG) \
+  {ID + KIND, #F "<" TAG ">", DLBB_FN(F<KIND>), kPP6Lds, kThreads2}
+static const GemmKernel kKernels[] = {
+    {GK_NONE, "none"},
+    DLBB_ROW(GK_NT_128, gemm_bf16_nt_kernel, 4 * kTileBytes, kThreads),
+    DLBB_ROW(GK_NT_256_DEEP, gemm_bf16_nt_256_deep, 2 * kBuf2Bytes, kThreads2),
+    DLBB_PP_ROW(GK_NT_256_PP, gemm_bf16_nt_256_pingpong3),
+    DLBB_PP_ROW(GK_NT_256_PP_BAL, gemm_bf16_nt_256_pingpong3_bal),
+    DLBB_ROW(GK_NT_192_PP, gemm_bf16_nt_192_pingpong3, kPP192Lds, kThreads2),
+    DLBB_ROW(GK_NT_192_PP_BAL, gemm_bf16_nt_192_pingpong3_bal, kPP192Lds, kThreads2),
+    {GK_NT_192_SPREAD, "gemm_bf16_nt_192_pp_spread", DLBB_FN(gemm_bf16_nt_192_pp_spread<12>),
+     kPP192Lds, kThreads2},
+    {GK_NT_192_SPREAD_BAL, "gemm_bf16_nt_192_pp_spread_bal",
+     DLBB_FN(gemm_bf16_nt_192_pp_spread_bal<12>), kPP192Lds, kThreads2},
+    DLBB_ROW(GK_NT_256_STREAMK, gemm_bf16_nt_256_streamk, kPP6Lds, kThreads2),
+    DLBB_ROW(GK_NT_256_STREAMK_BAL, gemm_bf16_nt_256_streamk_bal, kPP6Lds, kThreads2),
+    DLBB_PP_ROW(GK_NN_256_PP, gemm_bf16_nn_256_pingpong3),
+    DLBB_PP_ROW(GK_NN_256_PP_BAL, gemm_bf16_nn_256_pingpong3_bal),
+    DLBB_PP_ROW(GK_TN_256_PP, gemm_bf16_tn_256_pingpong3),
+    DLBB_PP_ROW(GK_TN_256_PP_BAL, gemm_bf16_tn_256_pingpong3_bal),
+    {},                                                                          // 15
+    DLBB_LEAN_ROW(GK_NT_256_PERSIST, gemm_bf16_nt_256_pp_persist, PP_PLAIN, "plain"),
+    DLBB_LEAN_ROW(GK_NT_256_PERSIST, gemm_bf16_nt_256_pp_persist, PP_BIAS, "bias"),
+    DLBB_LEAN_ROW(GK_NT_256_PERSIST, gemm_bf16_nt_256_pp_persist, PP_BIAS_GELU_TANH,
+                  "bias_gelu_tanh"),
+    DLBB_LEAN_ROW(GK_NT_256_PERSIST, gemm_bf16_nt_256_pp_persist, PP_BIAS_GELU_ERF,
+                  "bias_gelu_erf"),
+    {}, {}, {}, {},                                                              // 20 .. 23
+    DLBB_LEAN_ROW(GK_NT_256_PERSIST_BAL, gemm_bf16_nt_256_pp_persist_bal, PP_PLAIN, "plain"),
+    DLBB_LEAN_ROW(GK_NT_256_PERSIST_BAL, gemm_bf16_nt_256_pp_persist_bal, PP_BIAS, "bias"),
+    DLBB_LEAN_ROW(GK_NT_256_PERSIST_BAL, gemm_bf16_nt_256_pp_persist_bal, PP_BIAS_GELU_TANH,
+                  "bias_gelu_tanh"),
+    DLBB_LEAN_ROW(GK_NT_256_PERSIST_BAL, gemm_bf16_nt_256_pp_persist_bal, PP_BIAS_GELU_ERF,
+                  "bias_gelu_erf"),
+    {}, {}, {}, {},                                                              // 28 .. 31
+    DLBB_LEAN_ROW(GK_NN_256_PERSIST_BAL, gemm_bf16_nn_256_pp_persist_bal, PP_PLAIN, "plain"),
+    {}, {}, {},                                                                  // 33 .. 35
+    DLBB_LEAN_ROW(GK_NN_256_PERSIST_BAL, gemm_bf16_nn_256_pp_persist_bal, PP_DGELU_TANH,
+                  "dgelu_tanh"),
+    DLBB_LEAN_ROW(GK_NN_256_PERSIST_BAL, gemm_bf16_nn_256_pp_persist_bal, PP_DGELU_ERF,
+                  "dgelu_erf"),
+};
+#undef DLBB_LEAN_ROW
+#undef DLBB_PP_ROW
+#undef DLBB_ROW
+#undef DLBB_FN
+constexpr int kNumKernels = sizeof(kKernels) / sizeof(kKernels[0]);
+static_assert(kNumKernels == GK_NN_256_PERSIST_BAL + PP_DGELU_ERF + 1, "one row per id, gaps empty");
+
+// The kernel `id`, or with `bal` its balanced-DMA twin, `bal_step` ids further.
+static const GemmKernel& pick(int id, bool bal = false, int bal_step = 1) {
+  return kKernels[id + (bal ? bal_step : 0)];
+}
+
 static int dlbb_gemm_last = GK_NONE;
 
 DLBB_API int dlbb_gemm_last_kernel() { return dlbb_gemm_last; }
 
+// A row is found at its id (an empty or misplaced row reads "unknown"), its twin at id + kGkStamped.
 DLBB_API const char* dlbb_gemm_kernel_name(int id) {
-  switch (id) {
-    case GK_NONE: return "none";
-    case GK_NT_128: return "gemm_bf16_nt_kernel";
-    case GK_NT_256_DEEP: return "gemm_bf16_nt_256_deep";
-    case GK_NT_256_PP: return "gemm_bf16_nt_256_pingpong3";
-    case GK_NT_256_PP_BAL: return "gemm_bf16_nt_256_pingpong3_bal";
-    case GK_NT_192_PP: return "gemm_bf16_nt_192_pingpong3";
-    case GK_NT_192_PP_BAL: return "gemm_bf16_nt_192_pingpong3_bal";
-    case GK_NT_192_SPREAD: return "gemm_bf16_nt_192_pp_spread";
-    case GK_NT_192_SPREAD_BAL: return "gemm_bf16_nt_192_pp_spread_bal";
-    case GK_NT_256_STREAMK: return "gemm_bf16_nt_256_streamk";
-    case GK_NT_256_STREAMK_BAL: return "gemm_bf16_nt_256_streamk_bal";
-    case GK_NN_256_PP: return "gemm_bf16_nn_256_pingpong3";
-    case GK_NN_256_PP_BAL: return "gemm_bf16_nn_256_pingpong3_bal";
-    case GK_TN_256_PP: return "gemm_bf16_tn_256_pingpong3";
-    case GK_TN_256_PP_BAL: return "gemm_bf16_tn_256_pingpong3_bal";
-    case GK_NT_256_PERSIST + PP_PLAIN: return "gemm_bf16_nt_256_pp_persist<plain>";
-    case GK_NT_256_PERSIST + PP_BIAS: return "gemm_bf16_nt_256_pp_persist<bias>";
-    case GK_NT_256_PERSIST + PP_BIAS_GELU_TANH: return "gemm_bf16_nt_256_pp_persist<bias_gelu_tanh>";
-    case GK_NT_256_PERSIST + PP_BIAS_GELU_ERF: return "gemm_bf16_nt_256_pp_persist<bias_gelu_erf>";
-    case GK_NT_256_PERSIST_BAL + PP_PLAIN: return "gemm_bf16_nt_256_pp_persist_bal<plain>";
-    case GK_NT_256_PERSIST_BAL + PP_BIAS: return "gemm_bf16_nt_256_pp_persist_bal<bias>";
-    case GK_NT_256_PERSIST_BAL + PP_BIAS_GELU_TANH:
-      return "gemm_bf16_nt_256_pp_persist_bal<bias_gelu_tanh>";
-    case GK_NT_256_PERSIST_BAL + PP_BIAS_GELU_ERF:
-      return "gemm_bf16_nt_256_pp_persist_bal<bias_gelu_erf>";
-    case GK_NN_256_PERSIST_BAL + PP_PLAIN: return "gemm_bf16_nn_256_pp_persist_bal<plain>";
-    case GK_NN_256_PERSIST_BAL + PP_DGELU_TANH:
-      return "gemm_bf16_nn_256_pp_persist_bal<dgelu_tanh>";
-    case GK_NN_256_PERSIST_BAL + PP_DGELU_ERF:
-      return "gemm_bf16_nn_256_pp_persist_bal<dgelu_erf>";
-    case kGkStamped + GK_NT_256_PP: return "gemm_bf16_nt_256_pingpong3_st";
-    case kGkStamped + GK_NT_256_PP_BAL: return "gemm_bf16_nt_256_pingpong3_bal_st";
-    case kGkStamped + GK_NN_256_PP: return "gemm_bf16_nn_256_pingpong3_st";
-    case kGkStamped + GK_NN_256_PP_BAL: return "gemm_bf16_nn_256_pingpong3_bal_st";
-    case kGkStamped + GK_TN_256_PP: return "gemm_bf16_tn_256_pingpong3_st";
-    case kGkStamped + GK_TN_256_PP_BAL: return "gemm_bf16_tn_256_pingpong3_bal_st";
-    default: return "unknown";
-  }
+  const int i = id >= kGkStamped ? id - kGkStamped : id;
+  if (i < 0 || i >= kNumKernels || kKernels[i].id != i) return "unknown";
+  const char* name = i == id ? kKernels[i].name : kKernels[i].name_st;
+  return name ? name : "unknown";
 }
 
-// Launch a ping-pong kernel, or its stamped twin when stamping is on (dlbb_stamps_set).
-#define DLBB_PP_LAUNCH(KERNEL, ID, KIND, GRID, ARGS)                                      \
-  do {                                                                                   \
-    const dim3 g_(GRID);                                                                 \
-    uint64_t* st_ = stamp_acquire(KIND, static_cast<int64_t>(g_.x) * g_.y);              \
-    dlbb_gemm_last = st_ ? kGkStamped + (ID) : (ID);                                     \
-    if (st_)                                                                             \
-      hipLaunchKernelGGL(KERNEL##_st, g_, dim3(kThreads2), kPP6Lds, stream, ARGS, st_);  \
-    else                                                                                 \
-      hipLaunchKernelGGL(KERNEL, g_, dim3(kThreads2), kPP6Lds, stream, ARGS);            \
-  } while (0)
+// The one launch site: records the kernel for dlbb_gemm_last_kernel() and launches it on `grid` —
+// or its stamped twin, when it has one, the caller names the StampKind of its records and
+// stamping is on (dlbb_stamps_set). arg2: the kernel's second argument (Stream-K's SkArgs).
+static int launch(const GemmKernel& k, dim3 grid, hipStream_t stream, GemmArgs a,
+                  int stamp_kind = 0, void* arg2 = nullptr) {
+  uint64_t* st = k.fn_st && stamp_kind
+                     ? stamp_acquire(stamp_kind, static_cast<int64_t>(grid.x) * grid.y) : nullptr;
+  dlbb_gemm_last = st ? kGkStamped + k.id : k.id;
+  void* argv[] = {&a, st ? static_cast<void*>(&st) : arg2};
+  (void)hipLaunchKernel(st ? k.fn_st : k.fn, grid, dim3(k.threads), argv, k.lds, stream);
+  return hipGetLastError();
+}
 
 static int dlbb_gemm_force_tile = 0;   // 0 = heuristic, 128 or 256 = force (A/B testing)
 
@@ -2194,6 +2230,70 @@ DLBB_API void dlbb_gemm_set_concurrent(int on) { dlbb_gemm_concurrent = on; }
 DLBB_API int dlbb_gemm_get_concurrent() { return dlbb_gemm_concurrent; }
 DLBB_API void dlbb_gemm_set_bal(int mode) { dlbb_gemm_bal = mode >= 0 && mode <= 2 ? mode : 2; }
 
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The GemmArgs of a call; vec_ok = every pointer and row the epilogue touches is 16-B aligned.
+static GemmArgs fill_args(const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
+                          int64_t ldc, int64_t M, int64_t N, int64_t K, const void* bias,
+                          const void* residual, int64_t ldr, void* preact, int epi,
+                          int out_f32) {
+  const int vec_ok = (ldc % 8 == 0) && al16(C) && (!preact || al16(preact)) &&
+                     (!(epi & EPI_READS_R) || (ldr % 8 == 0 && al16(residual))) &&
+                     (!(epi & EPI_BIAS) || al16(bias));
+  return GemmArgs{static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), C,
+                  static_cast<const uint16_t*>(bias), static_cast<const uint16_t*>(residual),
+                  static_cast<uint16_t*>(preact), M, N, K, lda, ldb, ldc, ldr, epi, out_f32,
+                  vec_ok, 0};
+}
+
+// What every layout refuses (hipErrorInvalidValue), else *a = the call's GemmArgs: a reduction
+// that is not whole K-tiles, operand rows that are not 16-byte aligned (the LDS-DMA reads 16 B),
+// an epilogue flag without the operand it reads. Shape and bound conditions of one layout or
+// tile stay with their entry point.
+static int gemm_args(GemmArgs* a, const void* A, int64_t lda, const void* B, int64_t ldb,
+                     void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, const void* bias,
+                     const void* residual, int64_t ldr, void* preact, int epi, int out_f32) {
+  if (K <= 0 || K % BK != 0 || lda % 8 || ldb % 8 || !al16(A) || !al16(B))
+    return hipErrorInvalidValue;
+  if ((epi & EPI_BIAS) && !bias) return hipErrorInvalidValue;
+  if ((epi & EPI_READS_R) && !residual) return hipErrorInvalidValue;
+  *a = fill_args(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, preact, epi, out_f32);
+  return hipSuccess;
+}
+
+// 32-bit buffer offsets within a panel of `rows` rows (a tile's height or width) of a
+// K-contiguous operand
+static bool panel_fits(int64_t ld, int64_t rows, int64_t K) {
+  return ld * 2 * rows + K * 2 < (1LL << 31);
+}
+
+// split-K partial reduce + cast (csrc/gemm_tn.hip): out[i] = sum_s ws[s * n + i]
+int dlbb_split_reduce_launch(const float* ws, void* out, int dt_f32, int64_t n, int split,
+                             hipStream_t stream);
+
+// Split-K of a plain product with ldc == N: the ping-pong `family` (its BAL twin by the slice
+// length) on (tiles, split), slice s writing fp32 partials to ws[s][M][N], then one pass that
+// sums them into C (bf16, or fp32 when reduce_f32). ws_bytes >= 0: refuse a workspace the
+// renormalised split does not fit in (NT-split; the NN and TN callers size ws themselves, -1).
+// A misaligned ws only clears vec_ok (NN relies on it; NT-split and TN refuse one beforehand).
+static int launch_split(int family, bool nn, int stamp_kind, int64_t tiles, hipStream_t stream,
+                        GemmArgs a, int split, float* ws, int64_t ws_bytes, int reduce_f32) {
+  const int nkt = static_cast<int>(a.K / BK);
+  if (!ws || a.epi != 0 || a.ldc != a.N || split > nkt) return hipErrorInvalidValue;
+  a.kt_split = (nkt + split - 1) / split;
+  split = (nkt + a.kt_split - 1) / a.kt_split;   // every slice starts inside the reduction
+  if (ws_bytes >= 0 && ws_bytes < static_cast<int64_t>(split) * a.M * a.N * 4)
+    return hipErrorInvalidValue;
+  void* const C = a.C;
+  a.C = ws;
+  a.out_f32 = 1;
+  a.vec_ok = al16(ws) && a.N % 8 == 0;
+  const dim3 g(static_cast<unsigned>(tiles), static_cast<unsigned>(split));
+  const int e = launch(pick(family, use_bal(a.kt_split, nn)), g, stream, a, stamp_kind);
+  if (e != hipSuccess) return e;
+  return dlbb_split_reduce_launch(ws, C, reduce_f32, a.M * a.N, split, stream);
+}
+
 // ---------------------------------------------------------------------------------------
 // Stream-K plan (pp_streamk_body) for an NT shape on `ncu` CUs: out = {grid, L, ws bytes,
 // counters}; returns 0 when the shape is outside the Stream-K contract (256² tiles below one
@@ -2220,7 +2320,7 @@ DLBB_API int dlbb_gemm_streamk_plan(int64_t M, int64_t N, int64_t K, int ncu, in
   return 1;
 }
 
-// Stream-K NT GEMM, the same result contract as dlbb_gemm_bf16_nt (every epilogue); `ws` /
+// Stream-K NT GEMM, the same result contract as dlbb_gemm_bf16_nt_v (every epilogue); `ws` /
 // `cnt` as planned by dlbb_gemm_streamk_plan(..., ncu = grid owner's CU count), cnt ZERO on
 // entry (left zero). Host contract as the ping-pong: M % 8 == 0, N % 64 == 0, 16-B aligned
 // A / B / ws rows, 32-bit offsets within a 256-row panel.
@@ -2234,44 +2334,28 @@ DLBB_API int dlbb_gemm_bf16_nt_streamk(const void* A, int64_t lda, const void* B
   int64_t plan[4];
   if (!dlbb_gemm_streamk_plan(M, N, K, ncu, plan)) return hipErrorInvalidValue;
   if (!ws || !cnt || ws_bytes < plan[2] || ncnt < plan[3]) return hipErrorInvalidValue;
-  if (lda % 8 || ldb % 8 || M % 8 || N % 64 || M < 8) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) |
-       reinterpret_cast<uintptr_t>(ws)) & 15)
+  GemmArgs a;
+  if (gemm_args(&a, A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, preact, epi, out_f32))
     return hipErrorInvalidValue;
-  if (lda * 2 * 256 + K * 2 >= (1LL << 31) || ldb * 2 * 256 + K * 2 >= (1LL << 31) ||
-      plan[2] >= (1LL << 32))
+  if (M % 8 || N % 64 || M < 8 || !al16(ws)) return hipErrorInvalidValue;
+  if (!panel_fits(lda, BM2, K) || !panel_fits(ldb, BN2, K) || plan[2] >= (1LL << 32))
     return hipErrorInvalidValue;
-  if ((epi & EPI_BIAS) && !bias) return hipErrorInvalidValue;
-  if ((epi & EPI_READS_R) && !residual) return hipErrorInvalidValue;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const int vec_ok = (ldc % 8 == 0) && al16(C) && (!preact || al16(preact)) &&
-                     (!(epi & EPI_READS_R) || (ldr % 8 == 0 && al16(residual))) &&
-                     (!(epi & EPI_BIAS) || al16(bias));
-  GemmArgs a{static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), C,
-             static_cast<const uint16_t*>(bias), static_cast<const uint16_t*>(residual),
-             static_cast<uint16_t*>(preact), M, N, K, lda, ldb, ldc, ldr, epi, out_f32,
-             vec_ok, 0};
   SkArgs s{static_cast<float*>(ws), cnt, static_cast<int>(plan[1]), static_cast<int>(K / BK)};
-  const dim3 g(static_cast<unsigned>(plan[0])), b(kThreads2);
-  const bool bal = use_bal(plan[1], false);
-  dlbb_gemm_last = bal ? GK_NT_256_STREAMK_BAL : GK_NT_256_STREAMK;
-  if (bal)
-    hipLaunchKernelGGL(gemm_bf16_nt_256_streamk_bal, g, b, kPP6Lds, stream, a, s);
-  else
-    hipLaunchKernelGGL(gemm_bf16_nt_256_streamk, g, b, kPP6Lds, stream, a, s);
-  return hipGetLastError();
+  return launch(pick(GK_NT_256_STREAMK, use_bal(plan[1], false)),
+                dim3(static_cast<unsigned>(plan[0])), stream, a, 0, &s);
 }
 
 // Diagnostic: one plain bf16 NT GEMM on the balanced ping-pong (nj = 4: 256², 3: 256 x 192) with
 // per-workgroup phase stamps (4 u64 each: start, first MFMA, K-loop end, stores end) into recs
-// (gridDim.x records). Contract as the ping-pong; no autotuning, no epilogue.
+// (gridDim.x records). Contract as the ping-pong, which the caller keeps (tools/diag): only the
+// tiling is checked here, and the vector epilogue is taken. No autotuning, no epilogue.
 DLBB_API int dlbb_gemm_nt_phase_probe(const void* A, int64_t lda, const void* B, int64_t ldb,
                                       void* C, int64_t M, int64_t N, int64_t K, int nj,
                                       uint64_t* recs, hipStream_t stream) {
   if (M % 8 || (nj == 3 ? N % 192 : N % 64) || K % BK || K < 2 * BK || !recs)
     return hipErrorInvalidValue;
-  GemmArgs a{static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), C, nullptr,
-             nullptr, nullptr, M, N, K, lda, ldb, N, 0, 0, 0, 1, 0};
+  GemmArgs a = fill_args(A, lda, B, ldb, C, N, M, N, K, nullptr, nullptr, 0, nullptr, 0, 0);
+  a.vec_ok = 1;
   const int64_t tiles = ((M + BM2 - 1) / BM2) * ((N + 64 * nj - 1) / (64 * nj));
   if (nj == 3)
     hipLaunchKernelGGL(gemm_nt_pp192_phases, dim3(static_cast<unsigned>(tiles)), dim3(kThreads2),
@@ -2290,66 +2374,31 @@ DLBB_API int dlbb_gemm_nt_phase_probe(const void* A, int64_t lda, const void* B,
 DLBB_API int dlbb_gemm_bf16_nt_v(const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
                                  int64_t ldc, int64_t M, int64_t N, int64_t K, const void* bias,
                                  const void* residual, int64_t ldr, void* preact, int epi,
-                                 int out_f32, int variant, hipStream_t stream);
-
-DLBB_API int dlbb_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
-                               int64_t ldc, int64_t M, int64_t N, int64_t K, const void* bias,
-                               const void* residual, int64_t ldr, void* preact, int epi,
-                               int out_f32, hipStream_t stream) {
-  return dlbb_gemm_bf16_nt_v(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, preact, epi,
-                             out_f32, 0, stream);
-}
-
-DLBB_API int dlbb_gemm_bf16_nt_v(const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
-                                 int64_t ldc, int64_t M, int64_t N, int64_t K, const void* bias,
-                                 const void* residual, int64_t ldr, void* preact, int epi,
                                  int out_f32, int variant, hipStream_t stream) {
   if (M <= 0 || N <= 0) return hipSuccess;
-  if (K <= 0 || K % BK != 0) return hipErrorInvalidValue;
-  if (lda % 8 || ldb % 8) return hipErrorInvalidValue;          // 16-byte rows for glds
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15)
+  GemmArgs a;
+  if (gemm_args(&a, A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, preact, epi, out_f32))
     return hipErrorInvalidValue;
-  if ((epi & EPI_BIAS) && !bias) return hipErrorInvalidValue;
-  if ((epi & EPI_READS_R) && !residual) return hipErrorInvalidValue;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const int vec_ok = (ldc % 8 == 0) && al16(C) && (!preact || al16(preact)) &&
-                     (!(epi & EPI_READS_R) || (ldr % 8 == 0 && al16(residual))) &&
-                     (!(epi & EPI_BIAS) || al16(bias));
-  GemmArgs a{static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), C,
-             static_cast<const uint16_t*>(bias), static_cast<const uint16_t*>(residual),
-             static_cast<uint16_t*>(preact), M, N, K, lda, ldb, ldc, ldr, epi, out_f32,
-             vec_ok, 0};
-  const int64_t tiles256 = ((M + BM2 - 1) / BM2) * ((N + BN2 - 1) / BN2);
+  const int64_t nkt = K / BK, rows256 = (M + BM2 - 1) / BM2;
+  const int64_t tiles256 = rows256 * ((N + BN2 - 1) / BN2);
+  const bool bal = use_bal(nkt, false);
+  // 256 x 192 tiles: whole in N, 32-bit buffer offsets within a panel of A and of B
+  const bool fits192 = N % 192 == 0 && panel_fits(lda, BM2, K) && panel_fits(ldb, 192, K);
   // variant 2: persistent 256 x 192 with spread C stores (plain bf16 output only, >= 9 K-tiles,
   // 8-byte aligned rows; pp192_spread_body); anything else falls back to variant 1
-  if (variant == 2 && epi == 0 && !preact && !out_f32 && vec_ok && persist_enabled() &&
-      N % 192 == 0 && M % 16 == 0 && M >= 16 && K / BK >= spread_iters(12) + 2 &&
-      lda * 2 * 256 + K * 2 < (1LL << 31) && ldb * 2 * 192 + K * 2 < (1LL << 31)) {
-    const int64_t tiles = ((M + BM2 - 1) / BM2) * (N / 192);
+  if (variant == 2 && epi == 0 && !preact && !out_f32 && a.vec_ok && persist_enabled() &&
+      fits192 && M % 16 == 0 && M >= 16 && nkt >= spread_iters(12) + 2) {
+    const int64_t tiles = rows256 * (N / 192);
     const int64_t grid = tiles < num_cus() ? tiles : num_cus();
-    const dim3 g(static_cast<unsigned>(grid)), b(kThreads2);
-    const bool bal = use_bal(K / BK, false);
-    dlbb_gemm_last = bal ? GK_NT_192_SPREAD_BAL : GK_NT_192_SPREAD;
-    if (bal) hipLaunchKernelGGL(gemm_bf16_nt_192_pp_spread_bal<12>, g, b, kPP192Lds, stream, a);
-    else hipLaunchKernelGGL(gemm_bf16_nt_192_pp_spread<12>, g, b, kPP192Lds, stream, a);
-    return hipGetLastError();
+    return launch(pick(GK_NT_192_SPREAD, bal), dim3(static_cast<unsigned>(grid)), stream, a);
   }
   if (variant == 2) variant = 1;
-  if (variant == 1 && N % 192 == 0 && M % 8 == 0 && M >= 8 &&
-      lda * 2 * 256 + K * 2 < (1LL << 31) && ldb * 2 * 192 + K * 2 < (1LL << 31)) {
-    const dim3 g(static_cast<unsigned>(((M + BM2 - 1) / BM2) * (N / 192))), b(kThreads2);
-    const bool bal = use_bal(K / BK, false);
-    dlbb_gemm_last = bal ? GK_NT_192_PP_BAL : GK_NT_192_PP;
-    if (bal)
-      hipLaunchKernelGGL(gemm_bf16_nt_192_pingpong3_bal, g, b, kPP192Lds, stream, a);
-    else
-      hipLaunchKernelGGL(gemm_bf16_nt_192_pingpong3, g, b, kPP192Lds, stream, a);
-    return hipGetLastError();
-  }
+  if (variant == 1 && fits192 && M % 8 == 0 && M >= 8)
+    return launch(pick(GK_NT_192_PP, bal), dim3(static_cast<unsigned>(rows256 * (N / 192))),
+                  stream, a);
   // the 256^2 schedule needs >= ~1 workgroup per CU to fill the chip; otherwise 128^2 tiles
   const int force = dlbb_gemm_force_tile;
   if (force == 256 || (force != 128 && tiles256 >= 192)) {
-    const dim3 g(static_cast<unsigned>(tiles256)), b(kThreads2);
     int mode = dlbb_gemm_stagger == 10 || dlbb_gemm_stagger == 3 ? dlbb_gemm_stagger : 6;
     // default ping-pong on a multi-round grid with a short reduction: the persistent form
     // (tools/gemm_ab.py, profiles/r03_gemm/persistent_ab.jsonl, plain bf16: +6.6 % at
@@ -2358,7 +2407,7 @@ DLBB_API int dlbb_gemm_bf16_nt_v(const void* A, int64_t lda, const void* B, int6
     // lean epilogue kinds (bf16 output, vector stores, nothing read but the bias): plain, bias,
     // bias -> GELU with an optional pre-activation store; -1 = the general epilogue only
     int lean = -1;
-    if (!out_f32 && vec_ok) {
+    if (!out_f32 && a.vec_ok) {
       if (epi == 0 && !preact) lean = PP_PLAIN;
       else if (epi == EPI_BIAS && !preact) lean = PP_BIAS;
       else if (epi == (EPI_BIAS | EPI_GELU_TANH)) lean = PP_BIAS_GELU_TANH;
@@ -2366,56 +2415,36 @@ DLBB_API int dlbb_gemm_bf16_nt_v(const void* A, int64_t lda, const void* B, int6
     }
     if (lean > PP_PLAIN && !persist_epi_enabled()) lean = -1;
     if (mode == 6 && lean >= 0 && persist_enabled() && tiles256 > num_cus() &&
-        K / BK <= kPersistMaxKTiles)
+        nkt <= kPersistMaxKTiles)
       mode = 10;
     // persistent ping-pong (mode 10): the ping-pong contract, at least two K-tiles and a lean
     // epilogue
     if (mode == 10 && (K < 2 * BK || lean < 0)) mode = 6;
     // ping-pong contract: 8-row A groups and 64-row B blocks wholly in or out (uniform clamps),
     // 32-bit buffer offsets within a 256-row panel; otherwise the deep-pipeline kernel
-    if ((mode == 6 || mode == 10) &&
-        !(M % 8 == 0 && N % 64 == 0 && M >= 8 && lda * 2 * 256 + K * 2 < (1LL << 31) &&
-          ldb * 2 * 256 + K * 2 < (1LL << 31)))
+    if ((mode == 6 || mode == 10) && !(M % 8 == 0 && N % 64 == 0 && M >= 8 &&
+                                       panel_fits(lda, BM2, K) && panel_fits(ldb, BN2, K)))
       mode = 3;
     if (mode == 10) {
       const int64_t grid = tiles256 < num_cus() ? tiles256 : num_cus();
-      const dim3 gp(static_cast<unsigned>(grid)), bp(kThreads2);
-      const bool bal = use_bal(K / BK, false);
-#define DLBB_PP_PERSIST_LAUNCH(L)                                                          \
-  do {                                                                                     \
-    dlbb_gemm_last = (bal ? GK_NT_256_PERSIST_BAL : GK_NT_256_PERSIST) + (L);              \
-    if (bal) hipLaunchKernelGGL(gemm_bf16_nt_256_pp_persist_bal<L>, gp, bp, kPP6Lds, stream, a); \
-    else hipLaunchKernelGGL(gemm_bf16_nt_256_pp_persist<L>, gp, bp, kPP6Lds, stream, a);   \
-  } while (0)
-      switch (lean) {
-        case PP_BIAS: DLBB_PP_PERSIST_LAUNCH(PP_BIAS); break;
-        case PP_BIAS_GELU_TANH: DLBB_PP_PERSIST_LAUNCH(PP_BIAS_GELU_TANH); break;
-        case PP_BIAS_GELU_ERF: DLBB_PP_PERSIST_LAUNCH(PP_BIAS_GELU_ERF); break;
-        default: DLBB_PP_PERSIST_LAUNCH(PP_PLAIN); break;
-      }
-#undef DLBB_PP_PERSIST_LAUNCH
-      return hipGetLastError();
+      return launch(pick(GK_NT_256_PERSIST + lean, bal, GK_NT_256_PERSIST_BAL - GK_NT_256_PERSIST),
+                    dim3(static_cast<unsigned>(grid)), stream, a);
     }
-    if (mode == 6 && use_bal(K / BK, false)) {
-      DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3_bal, GK_NT_256_PP_BAL, STAMP_GEMM_NT, g, a);
-    } else if (mode == 6) {
-      DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3, GK_NT_256_PP, STAMP_GEMM_NT, g, a);
-    } else {
-      dlbb_gemm_last = GK_NT_256_DEEP;
-      hipLaunchKernelGGL(gemm_bf16_nt_256_deep, g, b, 2 * kBuf2Bytes, stream, a);
-    }
-    return hipGetLastError();
+    return launch(mode == 6 ? pick(GK_NT_256_PP, bal) : pick(GK_NT_256_DEEP),
+                  dim3(static_cast<unsigned>(tiles256)), stream, a, STAMP_GEMM_NT);
   }
   const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  dlbb_gemm_last = GK_NT_128;
-  hipLaunchKernelGGL(gemm_bf16_nt_kernel, dim3(static_cast<unsigned>(tiles)), dim3(kThreads),
-                     4 * kTileBytes, stream, a);
-  return hipGetLastError();
+  return launch(pick(GK_NT_128), dim3(static_cast<unsigned>(tiles)), stream, a);
 }
 
-// split-K partial reduce + cast (csrc/gemm_tn.hip): out[i] = sum_s ws[s * n + i]
-int dlbb_split_reduce_launch(const float* ws, void* out, int dt_f32, int64_t n, int split,
-                             hipStream_t stream);
+// variant 0 (tests/native/host_checks.cpp calls it)
+DLBB_API int dlbb_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
+                               int64_t ldc, int64_t M, int64_t N, int64_t K, const void* bias,
+                               const void* residual, int64_t ldr, void* preact, int epi,
+                               int out_f32, hipStream_t stream) {
+  return dlbb_gemm_bf16_nt_v(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, preact, epi,
+                             out_f32, 0, stream);
+}
 
 // dgrad GEMM: C[M, N] = epilogue(A[M, K] · B[K, N]), B row-major [K][N] (a Linear weight
 // [out, in] is exactly this for dX = dY · W). Ping-pong 256^2 schedule with transposed-read B.
@@ -2424,77 +2453,35 @@ DLBB_API int dlbb_gemm_bf16_nn(const void* A, int64_t lda, const void* B, int64_
                                const void* residual, int64_t ldr, void* preact, int epi,
                                int out_f32, int split, float* ws, hipStream_t stream) {
   if (M <= 0 || N <= 0) return hipSuccess;
-  if (K <= 0 || K % BK != 0 || N % BN2 != 0 || M % 8 != 0) return hipErrorInvalidValue;
-  if (lda % 8 || ldb % 8 || ldb < N || lda < K) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15)
+  GemmArgs a;
+  if (gemm_args(&a, A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, preact, epi, out_f32))
     return hipErrorInvalidValue;
+  if (N % BN2 != 0 || M % 8 != 0 || ldb < N || lda < K) return hipErrorInvalidValue;
   // 32-bit buffer offsets: a 256-row panel of A, all K rows of B
-  if (lda * 2 * 256 + K * 2 >= (1LL << 31) || K * ldb * 2 >= (1LL << 31))
-    return hipErrorInvalidValue;
-  if ((epi & EPI_BIAS) && !bias) return hipErrorInvalidValue;
-  if ((epi & EPI_READS_R) && !residual) return hipErrorInvalidValue;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const int vec_ok = (ldc % 8 == 0) && al16(C) && (!preact || al16(preact)) &&
-                     (!(epi & EPI_READS_R) || (ldr % 8 == 0 && al16(residual))) &&
-                     (!(epi & EPI_BIAS) || al16(bias));
-  GemmArgs a{static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), C,
-             static_cast<const uint16_t*>(bias), static_cast<const uint16_t*>(residual),
-             static_cast<uint16_t*>(preact), M, N, K, lda, ldb, ldc, ldr, epi, out_f32,
-             vec_ok, 0};
+  if (!panel_fits(lda, BM2, K) || K * ldb * 2 >= (1LL << 31)) return hipErrorInvalidValue;
   const int64_t tiles256 = ((M + BM2 - 1) / BM2) * (N / BN2);
   const int nkt = static_cast<int>(K / BK);
   if (split > 1) {
     // split-K for grids below one workgroup per CU (the LM-head dX: 192 tiles, 786 K-tiles):
     // fp32 partials [split][M][N] in ws, then one reduce + bf16 cast pass. Plain product only.
-    if (!ws || epi != 0 || out_f32 || ldc != N || split > nkt) return hipErrorInvalidValue;
-    a.kt_split = (nkt + split - 1) / split;
-    split = (nkt + a.kt_split - 1) / a.kt_split;   // every slice starts inside the reduction
-    a.C = ws;
-    a.out_f32 = 1;
-    a.vec_ok = (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && N % 8 == 0;
-    if (use_bal(a.kt_split, true))
-      DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3_bal, GK_NN_256_PP_BAL, STAMP_GEMM_NN,
-                     dim3(static_cast<unsigned>(tiles256), split), a);
-    else
-      DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3, GK_NN_256_PP, STAMP_GEMM_NN,
-                     dim3(static_cast<unsigned>(tiles256), split), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return dlbb_split_reduce_launch(ws, C, 0, M * N, split, stream);
+    // NN alone reduces to bf16 whatever the caller asked (so fp32 output is refused) and takes
+    // a misaligned ws, with scalar partial stores; its caller sizes ws (no ws_bytes).
+    if (out_f32) return hipErrorInvalidValue;
+    return launch_split(GK_NN_256_PP, true, STAMP_GEMM_NN, tiles256, stream, a, split, ws, -1, 0);
   }
   // multi-round grid with a short reduction: the persistent form (plain bf16 or the GELU
   // backward, operands of the epilogue prefetched before the DMA drain; the GPT-2 MLP-proj dX,
   // 768 tiles x 12 K-tiles)
+  const int lean = epi == 0 ? PP_PLAIN
+                   : epi == EPI_DGELU_TANH ? PP_DGELU_TANH
+                   : epi == EPI_DGELU_ERF ? PP_DGELU_ERF : -1;
   if (persist_enabled() && persist_epi_enabled() && tiles256 > num_cus() && nkt >= 2 &&
-      nkt <= kPersistMaxKTiles && use_bal(nkt, true) && !out_f32 && vec_ok && !preact) {
-    const int lean = epi == 0 ? PP_PLAIN
-                     : epi == EPI_DGELU_TANH ? PP_DGELU_TANH
-                     : epi == EPI_DGELU_ERF ? PP_DGELU_ERF : -1;
-    const dim3 gp(static_cast<unsigned>(num_cus())), bp(kThreads2);
-    if (lean >= 0) dlbb_gemm_last = GK_NN_256_PERSIST_BAL + lean;
-    switch (lean) {
-      case PP_PLAIN:
-        hipLaunchKernelGGL(gemm_bf16_nn_256_pp_persist_bal<PP_PLAIN>, gp, bp, kPP6Lds, stream, a);
-        return hipGetLastError();
-      case PP_DGELU_TANH:
-        hipLaunchKernelGGL(gemm_bf16_nn_256_pp_persist_bal<PP_DGELU_TANH>, gp, bp, kPP6Lds,
-                           stream, a);
-        return hipGetLastError();
-      case PP_DGELU_ERF:
-        hipLaunchKernelGGL(gemm_bf16_nn_256_pp_persist_bal<PP_DGELU_ERF>, gp, bp, kPP6Lds,
-                           stream, a);
-        return hipGetLastError();
-      default:
-        break;
-    }
-  }
-  if (use_bal(nkt, true))
-    DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3_bal, GK_NN_256_PP_BAL, STAMP_GEMM_NN,
-                   dim3(static_cast<unsigned>(tiles256)), a);
-  else
-    DLBB_PP_LAUNCH(gemm_bf16_nn_256_pingpong3, GK_NN_256_PP, STAMP_GEMM_NN,
-                   dim3(static_cast<unsigned>(tiles256)), a);
-  return hipGetLastError();
+      nkt <= kPersistMaxKTiles && use_bal(nkt, true) && !out_f32 && a.vec_ok && !preact &&
+      lean >= 0)
+    return launch(pick(GK_NN_256_PERSIST_BAL + lean), dim3(static_cast<unsigned>(num_cus())),
+                  stream, a);
+  return launch(pick(GK_NN_256_PP, use_bal(nkt, true)), dim3(static_cast<unsigned>(tiles256)),
+                stream, a, STAMP_GEMM_NN);
 }
 
 // Split-K NT GEMM, plain product to bf16 (C = A · B^T, ldc == N): the ping-pong on
@@ -2509,36 +2496,19 @@ DLBB_API int dlbb_gemm_bf16_nt_split(const void* A, int64_t lda, const void* B, 
                                      int split, int tile192, float* ws, int64_t ws_bytes,
                                      hipStream_t stream) {
   if (M <= 0 || N <= 0) return hipSuccess;
-  if (K <= 0 || K % BK != 0 || split < 2 || ldc != N) return hipErrorInvalidValue;
-  if (lda % 8 || ldb % 8 || M % 8 || M < 8 || N % 64) return hipErrorInvalidValue;
-  if (tile192 && N % 192) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) |
-       reinterpret_cast<uintptr_t>(ws)) & 15)
+  GemmArgs a;
+  if (split < 2 || gemm_args(&a, A, lda, B, ldb, C, ldc, M, N, K, nullptr, nullptr, 0, nullptr,
+                             0, 0))
     return hipErrorInvalidValue;
+  if (M % 8 || M < 8 || N % 64 || (tile192 && N % 192)) return hipErrorInvalidValue;
   const int bn = tile192 ? 192 : BN2;
-  if (lda * 2 * 256 + K * 2 >= (1LL << 31) || ldb * 2 * bn + K * 2 >= (1LL << 31))
-    return hipErrorInvalidValue;
-  const int nkt = static_cast<int>(K / BK);
-  if (split > nkt) return hipErrorInvalidValue;
-  GemmArgs a{static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), ws, nullptr,
-             nullptr, nullptr, M, N, K, lda, ldb, N, 0, 0, 1, N % 8 == 0 ? 1 : 0, 0};
-  a.kt_split = (nkt + split - 1) / split;
-  split = (nkt + a.kt_split - 1) / a.kt_split;   // every slice starts inside the reduction
-  if (!ws || ws_bytes < static_cast<int64_t>(split) * M * N * 4) return hipErrorInvalidValue;
+  if (!panel_fits(lda, BM2, K) || !panel_fits(ldb, bn, K)) return hipErrorInvalidValue;
+  // NT-split refuses a misaligned ws (as TN, unlike NN) and, alone, is told the size of ws:
+  // launch_split checks it against the split it renormalised
+  if (!al16(ws)) return hipErrorInvalidValue;
   const int64_t tiles = ((M + BM2 - 1) / BM2) * ((N + bn - 1) / bn);
-  const dim3 g(static_cast<unsigned>(tiles), static_cast<unsigned>(split)), b(kThreads2);
-  const bool bal = use_bal(a.kt_split, false);
-  if (tile192) {
-    dlbb_gemm_last = bal ? GK_NT_192_PP_BAL : GK_NT_192_PP;
-    if (bal) hipLaunchKernelGGL(gemm_bf16_nt_192_pingpong3_bal, g, b, kPP192Lds, stream, a);
-    else hipLaunchKernelGGL(gemm_bf16_nt_192_pingpong3, g, b, kPP192Lds, stream, a);
-  } else {
-    if (bal) DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3_bal, GK_NT_256_PP_BAL, STAMP_GEMM_NT, g, a);
-    else DLBB_PP_LAUNCH(gemm_bf16_nt_256_pingpong3, GK_NT_256_PP, STAMP_GEMM_NT, g, a);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return dlbb_split_reduce_launch(ws, C, 0, M * N, split, stream);
+  return launch_split(tile192 ? GK_NT_192_PP : GK_NT_256_PP, false, STAMP_GEMM_NT, tiles, stream,
+                      a, split, ws, ws_bytes, 0);
 }
 
 // weight-gradient GEMM on the 256^2 ping-pong: C[M, N] = epilogue(A[K, M]^T · B[K, N]) with
@@ -2552,44 +2522,23 @@ DLBB_API int dlbb_gemm_bf16_tn(const void* A, int64_t lda, const void* B, int64_
                                int64_t ldr, int epi, int out_f32, int split, float* ws,
                                hipStream_t stream) {
   if (M <= 0 || N <= 0) return hipSuccess;
-  if (K <= 0 || K % BK != 0 || M % 128 != 0 || N % BN2 != 0) return hipErrorInvalidValue;
-  if (lda % 8 || ldb % 8 || lda < M || ldb < N || ldc < N) return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15)
+  if (epi != 0 && epi != EPI_RESIDUAL) return hipErrorInvalidValue;
+  if (epi == EPI_RESIDUAL && out_f32) return hipErrorInvalidValue;
+  GemmArgs a;
+  if (gemm_args(&a, A, lda, B, ldb, C, ldc, M, N, K, nullptr, residual, ldr, nullptr, epi,
+                out_f32))
     return hipErrorInvalidValue;
+  if (M % 128 != 0 || N % BN2 != 0 || lda < M || ldb < N || ldc < N) return hipErrorInvalidValue;
   // 32-bit buffer offsets over all K rows of both operands
   if (K * lda * 2 >= (1LL << 31) || K * ldb * 2 >= (1LL << 31)) return hipErrorInvalidValue;
-  if (epi != 0 && epi != EPI_RESIDUAL) return hipErrorInvalidValue;
-  if (epi == EPI_RESIDUAL && (!residual || out_f32)) return hipErrorInvalidValue;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const int vec_ok = (ldc % 8 == 0) && al16(C) && (epi == 0 || (ldr % 8 == 0 && al16(residual)));
-  GemmArgs a{static_cast<const uint16_t*>(A), static_cast<const uint16_t*>(B), C, nullptr,
-             static_cast<const uint16_t*>(residual), nullptr, M, N, K, lda, ldb, ldc, ldr, epi,
-             out_f32, vec_ok, 0};
   const int64_t tiles256 = ((M + BM2 - 1) / BM2) * (N / BN2);
-  const int nkt = static_cast<int>(K / BK);
   if (split > 1) {
-    if (!ws || epi != 0 || ldc != N || split > nkt || (reinterpret_cast<uintptr_t>(ws) & 15))
-      return hipErrorInvalidValue;
-    const int dt_f32 = out_f32;
-    a.kt_split = (nkt + split - 1) / split;
-    split = (nkt + a.kt_split - 1) / a.kt_split;   // every slice starts inside the reduction
-    a.C = ws;
-    a.out_f32 = 1;
-    a.vec_ok = N % 8 == 0;
-    const dim3 g(static_cast<unsigned>(tiles256), static_cast<unsigned>(split));
-    if (use_bal(a.kt_split, true))
-      DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3_bal, GK_TN_256_PP_BAL, STAMP_GEMM_TN, g, a);
-    else
-      DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3, GK_TN_256_PP, STAMP_GEMM_TN, g, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return dlbb_split_reduce_launch(ws, C, dt_f32, M * N, split, stream);
+    // TN refuses a misaligned ws (unlike NN) and, alone, reduces into the caller's dtype; its
+    // caller sizes ws (no ws_bytes)
+    if (!al16(ws)) return hipErrorInvalidValue;
+    return launch_split(GK_TN_256_PP, true, STAMP_GEMM_TN, tiles256, stream, a, split, ws, -1,
+                        out_f32);
   }
-  if (use_bal(nkt, true))
-    DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3_bal, GK_TN_256_PP_BAL, STAMP_GEMM_TN,
-                   dim3(static_cast<unsigned>(tiles256)), a);
-  else
-    DLBB_PP_LAUNCH(gemm_bf16_tn_256_pingpong3, GK_TN_256_PP, STAMP_GEMM_TN,
-                   dim3(static_cast<unsigned>(tiles256)), a);
-  return hipGetLastError();
+  return launch(pick(GK_TN_256_PP, use_bal(K / BK, true)), dim3(static_cast<unsigned>(tiles256)),
+                stream, a, STAMP_GEMM_TN);
 }

@@ -608,6 +608,14 @@ DLBB_API int dlbb_gemm_wgrad_tile2(const void* A, int64_t lda, const void* B, in
                       bk, nullptr, 0, stream);
 }
 
+// 128 x 128 tiles (tests/native/host_checks.cpp calls it)
+DLBB_API int dlbb_gemm_wgrad(const void* A, int64_t lda, const void* B, int64_t ldb, void* out,
+                             int dt_out, int accumulate, float* ws, int M, int N, int K,
+                             int split, void* out_bias, hipStream_t stream) {
+  return dlbb_gemm_wgrad_tile2(A, lda, B, ldb, out, dt_out, accumulate, ws, M, N, K, split,
+                               out_bias, 128, 128, stream);
+}
+
 // As tile2, with the split-K combine done inside the launch by each tile's last-arriving
 // workgroup: `counters` = dlbb_gemm_wgrad_counters(N, K, bn, bk) ints, ZERO on entry (the
 // launch leaves them zero again), owned by one stream at a time. A one-split plain store still
@@ -621,13 +629,6 @@ DLBB_API int dlbb_gemm_wgrad_fused(const void* A, int64_t lda, const void* B, in
                       bk, counters, ncounters, stream);
 }
 
-DLBB_API int dlbb_gemm_wgrad_tile(const void* A, int64_t lda, const void* B, int64_t ldb,
-                                  void* out, int dt_out, int accumulate, float* ws, int M, int N,
-                                  int K, int split, void* out_bias, int bn, hipStream_t stream) {
-  return dlbb_gemm_wgrad_tile2(A, lda, B, ldb, out, dt_out, accumulate, ws, M, N, K, split,
-                               out_bias, bn, 128, stream);
-}
-
 // out (bf16, or fp32 when dt_f32) = sum over `split` fp32 slices of n elements (n % 8 == 0);
 // used by the NN dgrad's split-K (csrc/gemm.hip).
 int dlbb_split_reduce_launch(const float* ws, void* out, int dt_f32, int64_t n, int split,
@@ -638,11 +639,4 @@ int dlbb_split_reduce_launch(const float* ws, void* out, int dt_f32, int64_t n, 
   else
     tn::split_reduce_dispatch<DT_BF16>(ws, out, n, nullptr, 0, split, 0, stream);
   return hipGetLastError();
-}
-
-DLBB_API int dlbb_gemm_wgrad(const void* A, int64_t lda, const void* B, int64_t ldb, void* out,
-                             int dt_out, int accumulate, float* ws, int M, int N, int K,
-                             int split, void* out_bias, hipStream_t stream) {
-  return dlbb_gemm_wgrad_tile(A, lda, B, ldb, out, dt_out, accumulate, ws, M, N, K, split,
-                              out_bias, 128, stream);
 }

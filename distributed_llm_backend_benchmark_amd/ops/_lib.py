@@ -138,9 +138,6 @@ _SIGS = {
                               c_void_p, c_void_p]),
     "dlbb_gemm_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int,
                                 c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "dlbb_gemm_wgrad_tile": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int,
-                                     c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
-                                     c_int, c_void_p]),
     "dlbb_gemm_wgrad_tile2": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int,
                                      c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                      c_int, c_int, c_void_p]),

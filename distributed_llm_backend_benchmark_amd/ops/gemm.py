@@ -218,14 +218,16 @@ def _torch_linear(x2, w, bias, act, residual, out_dtype, preact):
     return y.to(out_dtype)
 
 
+def _epi_flags(act, bias, r2) -> int:
+    """The C entry points' ``epi`` of ``act(. + bias) + r2``."""
+    return (ACTS[act] | (EPI_BIAS if bias is not None else 0)
+            | (EPI_RESIDUAL if r2 is not None else 0))
+
+
 def _mfma_linear(x2, w, bias, act, r2, out, preact, variant: int = 0):
     M, K = x2.shape
     N = w.shape[0]
-    epi = ACTS[act]
-    if bias is not None:
-        epi |= EPI_BIAS
-    if r2 is not None:
-        epi |= EPI_RESIDUAL
+    epi = _epi_flags(act, bias, r2)
     check(_lib.lib().dlbb_gemm_bf16_nt_v(
         x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), N, M, N, K,
         _lib.ptr(bias), _lib.ptr(r2), r2.stride(0) if r2 is not None else 0,
@@ -260,8 +262,12 @@ def mfma192p_ok(M: int, N: int, K: int, plain: bool) -> bool:
 _NCU = {}
 
 
+def _dev_index(device) -> int:
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
 def _num_cus(device) -> int:
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = _dev_index(device)
     if idx not in _NCU:
         _NCU[idx] = torch.cuda.get_device_properties(idx).multi_processor_count
     return _NCU[idx]
@@ -278,22 +284,29 @@ def streamk_plan(M: int, N: int, K: int, ncu: int):
     return tuple(int(v) for v in out)
 
 
+def _stream_buffers(cache: dict, device: torch.device, *specs) -> tuple:
+    """The buffers of ``cache`` private to (device, current stream), one per spec ``(elements,
+    dtype, floor, zero)``: launches on one stream are ordered, so one set serves every call on
+    it. A buffer is grown on demand (to at least ``floor`` elements, never shrunk), with no
+    per-call allocation or memset. ``zero``: zero-filled when allocated — arrival counters,
+    which every launch leaves zero again; partial workspaces stay uninitialised."""
+    key = (_dev_index(device), _lib.stream(device))
+    bufs = list(cache.get(key, (None,) * len(specs)))
+    for i, (n, dtype, floor, zero) in enumerate(specs):
+        if bufs[i] is None or bufs[i].numel() < n:
+            bufs[i] = (torch.zeros if zero else torch.empty)(max(n, floor), dtype=dtype,
+                                                             device=device)
+    cache[key] = tuple(bufs)
+    return cache[key]
+
+
 _SK_WS = {}      # (device index, stream handle) -> (fp32 partial workspace, int32 counters)
 
 
 def _streamk_buffers(device: torch.device, ws_bytes: int, ncnt: int):
-    """Partial-block workspace and (tile, wave) arrival counters, private to the current stream
-    (launches on one stream are ordered; every launch leaves its counters zero), grown on
-    demand — one zero-fill per stream, no per-call allocation or memset."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, _lib.stream(device))
-    ws, cnt = _SK_WS.get(key, (None, None))
-    if ws is None or ws.numel() * 4 < ws_bytes:
-        ws = torch.empty(max(ws_bytes // 4, 1 << 20), dtype=torch.float32, device=device)
-    if cnt is None or cnt.numel() < ncnt:
-        cnt = torch.zeros(max(ncnt, 4096), dtype=torch.int32, device=device)
-    _SK_WS[key] = (ws, cnt)
-    return ws, cnt
+    """Partial-block workspace and (tile, wave) arrival counters of the Stream-K GEMM."""
+    return _stream_buffers(_SK_WS, device, (-(-ws_bytes // 4), torch.float32, 1 << 20, False),
+                           (ncnt, torch.int32, 4096, True))
 
 
 def _mfma_streamk_linear(x2, w, bias, act, r2, out, preact):
@@ -306,11 +319,7 @@ def _mfma_streamk_linear(x2, w, bias, act, r2, out, preact):
     plan = streamk_plan(M, N, K, ncu)
     if plan is None:
         return _mfma_linear(x2, w, bias, act, r2, out, preact)
-    epi = ACTS[act]
-    if bias is not None:
-        epi |= EPI_BIAS
-    if r2 is not None:
-        epi |= EPI_RESIDUAL
+    epi = _epi_flags(act, bias, r2)
     ws, cnt = _streamk_buffers(x2.device, plan[2], plan[3])
     check(_lib.lib().dlbb_gemm_bf16_nt_streamk(
         x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
@@ -354,13 +363,7 @@ def _mfma_split_linear(x2, w, bias, act, r2, out, preact):
             preact is not None or out.dtype != torch.bfloat16:   # outside: the default ping-pong
         return _mfma_linear(x2, w, bias, act, r2, out, preact)
     split, t192 = plan
-    idx = x2.device.index if x2.device.index is not None else torch.cuda.current_device()
-    key = (idx, _lib.stream(x2.device))
-    ws = _SPLIT_WS.get(key)
-    need = split * M * N
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.float32, device=x2.device)
-        _SPLIT_WS[key] = ws
+    ws, = _stream_buffers(_SPLIT_WS, x2.device, (split * M * N, torch.float32, 0, False))
     check(_lib.lib().dlbb_gemm_bf16_nt_split(
         x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), N, M, N, K,
         split, t192, ws.data_ptr(), ws.numel() * 4, _lib.stream(x2.device)),
@@ -427,11 +430,7 @@ def _mfma_skinny_linear(x2, w, bias, act, r2, out, preact):
             and out.is_contiguous()
             and (bias is None or (bias.dtype == bf16 and bias.is_contiguous()))
             and (r2 is None or (r2.dtype == bf16 and r2.stride(1) == 1))):
-        epi = ACTS[act]
-        if bias is not None:
-            epi |= EPI_BIAS
-        if r2 is not None:
-            epi |= EPI_RESIDUAL
+        epi = _epi_flags(act, bias, r2)
         dev = x2.device
         rc = _lib.lib().dlbb_gemm_bf16_nt_skinny(
             x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), M,
@@ -644,16 +643,8 @@ def wgrad_fused_reduce() -> bool:
 
 
 def _tile_counters(device: torch.device, n: int) -> torch.Tensor:
-    """Arrival counters for ``n`` tiles, private to the current stream: launches on one stream
-    are ordered, and every fused launch leaves its counters zero again, so one zero-filled
-    buffer per stream serves every call on it (grown, never shrunk)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, _lib.stream(device))
-    buf = _COUNTERS.get(key)
-    if buf is None or buf.numel() < n:
-        buf = torch.zeros(max(n, 4096), dtype=torch.int32, device=device)
-        _COUNTERS[key] = buf
-    return buf
+    """Arrival counters for ``n`` tiles of the fused weight-gradient reduce."""
+    return _stream_buffers(_COUNTERS, device, (n, torch.int32, 4096, True))[0]
 
 
 # Cap on the default split-K of the weight gradient (None: no cap). The default fills about one
@@ -769,8 +760,7 @@ def _wgrad_pp(dy2, x2, out, accumulate, split=None, bias_out=None):
     K = x2.shape[1]
     head, tsplit = (N, 1)
     if not accumulate:
-        ncu = torch.cuda.get_device_properties(dy2.device).multi_processor_count
-        head, tsplit = pp_tail_plan(M, N, K, ncu)
+        head, tsplit = pp_tail_plan(M, N, K, _num_cus(dy2.device))
     _pp_launch(dy2, x2, out, accumulate, 0, head, 1)
     if head < N:
         _pp_launch(dy2, x2, out, accumulate, head, N, tsplit)
@@ -910,16 +900,13 @@ def _dgrad_hip(dy2, w, out, split=None, dgelu=None):
     return out
 
 
-_GELU_APPROX = {"gelu": 0, "gelu_erf": 0, "gelu_tanh": 1}
-
-
 def _dgrad_blas(dy2, w, out, split=None, dgelu=None):
     if dgelu is None:
         return torch.matmul(dy2, w, out=out)
     u, act = dgelu
     dg = torch.matmul(dy2, w)
     check(_lib.lib().dlbb_bias_gelu_bwd(dg.data_ptr(), u.data_ptr(), None, out.data_ptr(), None,
-                                        out.shape[0], out.shape[1], _GELU_APPROX[act],
+                                        out.shape[0], out.shape[1], _APPROX[act],
                                         _lib.stream(dy2.device)), "bias_gelu_bwd")
     return out
 
