@@ -27,6 +27,12 @@ one e8m0 scale per 32 k; ``ops.mxfp4``) the same way: suffix ``_decode<N>_w4``. 
 codes with one fp32 scale per cached row (``ops.decode``): suffix ``_kv8`` (after ``_w8`` / ``_w4``), the
 ``decode`` section carries ``kv_dtype`` and counts codes + scales in its cache and K / V bytes. It
 composes with ``--decode-weights fp8`` / ``mxfp4`` and needs decode tokens and a real attention (not ``slice``).
+``--prompt-lens L0,L1,...`` (``execution.prompt_lengths``) makes the batch right-padded prompts of
+these lengths over a per-sequence KV cache (``ops.decode``): one value per batch row in ``[1,
+sequence_length]``; needs decode tokens and a real attention, composes with ``--kv-cache fp8`` and
+``--decode-weights``. The split grid is bounded by ``max + N``, the ``decode`` section carries
+``prompt_lengths`` and counts the K / V bytes of the per-row lengths, the suffix ``_ragged`` comes
+last. The captured step replays as before: the lengths are device memory.
 """
 
 from __future__ import annotations
@@ -109,6 +115,11 @@ def parse_args(argv=None):
                          "e4m3 codes with one fp32 scale per cached row, head_dim + 4 bytes per "
                          "row instead of 2 head_dim; not with attention slice (no cache); output "
                          "file gets the suffix _kv8")
+    ap.add_argument("--prompt-lens", default=None, metavar="L0,L1,...",
+                    help="with --decode: the batch is right-padded prompts of these lengths "
+                         "(execution.prompt_lengths), one per batch row in [1, sequence_length], "
+                         "decoded over a per-sequence KV cache; not with attention slice; output "
+                         "file gets the suffix _ragged")
     ap.add_argument("--max-len", type=int, default=None, metavar="L",
                     help="with --decode: positions of the KV cache (default sequence_length + N)")
     ap.add_argument("--check-dense", action="store_true",
@@ -189,6 +200,30 @@ def main(argv=None) -> int:
                    "attention sdpa or flash: attention slice keeps no K / V to quantise"))
         return 1
     prompt = int(config["input"]["sequence_length"])
+    if args.prompt_lens is not None:
+        try:
+            ex["prompt_lengths"] = [int(v) for v in args.prompt_lens.split(",")]
+        except ValueError:
+            print(f"ERROR: --prompt-lens takes integers L0,L1,..., got {args.prompt_lens!r}")
+            return 1
+    lens = ex.get("prompt_lengths")
+    if lens is not None:
+        # refused before any process group exists, like --kv-cache fp8
+        nb = int(config["input"]["batch_size"])
+        why = None
+        if not n_dec:
+            why = "decode tokens (--decode N): only the decode steps keep a KV cache"
+        elif ex.get("attention", "slice") == "slice":
+            why = "attention sdpa or flash: attention slice keeps no K / V"
+        elif len(lens) != nb:
+            why = f"one value per batch row: got {len(lens)} for batch_size {nb}"
+        elif any(not 1 <= int(v) <= prompt for v in lens):
+            why = f"values in [1, sequence_length {prompt}], got {lens}"
+        if why:
+            if os.environ.get("RANK", "0") == "0":
+                print(f"ERROR: --prompt-lens (execution.prompt_lengths) needs {why}")
+            return 1
+        lens = [int(v) for v in lens]
     max_len = int(args.max_len) if args.max_len else prompt + n_dec
     if n_dec and max_len < prompt + n_dec:
         print(f"ERROR: --max-len {max_len} < sequence_length {prompt} + {n_dec} decoded tokens")
@@ -295,14 +330,16 @@ def main(argv=None) -> int:
 
     # --decode: the forward fills a KV cache (emptied before every call) and N one-token steps
     # follow it; without it `forward` is the model itself, as before
-    cache = model.new_kv_cache(int(config["input"]["batch_size"]), max_len) if n_dec else None
+    cache = (model.new_kv_cache(int(config["input"]["batch_size"]), max_len,
+                                per_sequence=lens is not None) if n_dec else None)
     if cache is not None:
-        cache.len_bound = prompt + n_dec        # split grid of the decode kernel: final position
+        # split grid of the decode kernel: final position (of the longest row)
+        cache.len_bound = (max(lens) if lens else prompt) + n_dec
 
     def forward(x):
         if cache is None:
             return model(x)
-        return model(x, kv_cache=cache)
+        return model(x, kv_cache=cache, prompt_lens=lens)
 
     fwd_bytes = 0
     for _ in range(int(ex["warmup_iterations"])):
@@ -385,7 +422,7 @@ def main(argv=None) -> int:
     dec = None
     if cache is not None:
         dec = _DecodeRunner(model, cache, comm, prompt, n_dec, dataset.get_batch(),
-                            use_graph, ex)
+                            use_graph, ex, lens)
         if dec.graph_note and rank == 0:
             print(f"note: decode steps issued eagerly: {dec.graph_note}")
 
@@ -494,7 +531,7 @@ def main(argv=None) -> int:
             suffix += f"_{extra['gemm_dtype']}"
         if dec is not None:                    # never overwrites the prefill record
             suffix += f"_decode{n_dec}" + ("_w8" if w8 else "_w4" if w4 else "") + \
-                ("_kv8" if kv8 else "")
+                ("_kv8" if kv8 else "") + ("_ragged" if lens else "")
             d = results["decode"]
             print(f"  decode: {d['ms_per_token_mean']:.4f} ms/token ({d['timing_mode']}, "
                   f"attention {d['attention_path']}), {d['decode_tokens_per_s']:.0f} tokens/s, "
@@ -521,16 +558,24 @@ class _DecodeRunner:
     ``M = B`` shapes; then, where the forward was captured (``capturable``) and the attention
     reads the cache length from the device (our kernel, or the stateless stub), ONE step is
     captured at ``len_bound = prompt + N`` and replayed N times; otherwise the host issues the
-    steps. The N steps are timed by one device-event pair and by the host clock after a sync."""
+    steps. The N steps are timed by one device-event pair and by the host clock after a sync.
 
-    def __init__(self, model, cache, comm, prompt: int, n: int, batch, capturable: bool, ex):
+    ``lens`` (``--prompt-lens``): the prompts are right-padded to ``prompt`` and the cache is a
+    per-sequence one; row ``b`` starts at ``lens[b]`` and its first decode input is the output at
+    its last real token."""
+
+    def __init__(self, model, cache, comm, prompt: int, n: int, batch, capturable: bool, ex,
+                 lens=None):
         import torch
 
         from ..ops import _lib, fp8, mxfp4
         from ..ops import decode as dec_ops
 
         self.model, self.cache, self.comm = model, cache, comm
-        self.prompt, self.n = prompt, n
+        self.prompt, self.n, self.lens = prompt, n, lens
+        # row b's last real token of a padded prefill output (None: the last position)
+        self.last = (torch.tensor([v - 1 for v in lens], device=batch.device) if lens else None)
+        self.rows = torch.arange(batch.shape[0], device=batch.device) if lens else None
         self.gpu = comm.is_gpu
         attention = ex.get("attention", "slice")
         heads = model.num_heads // model.world_size
@@ -552,12 +597,12 @@ class _DecodeRunner:
 
         # warm: a prefill, then two eager steps at the first decode position
         cache.set_length(0)
-        y = model(batch, kv_cache=cache)
-        self.x.copy_(y[:, -1:])
+        y = model(batch, kv_cache=cache, prompt_lens=lens)
+        self.x.copy_(self._last_rows(y))
         b0, l0 = model.comm_bytes(), fp8.W8_LAUNCHES["count"]
         l4 = mxfp4.W4_LAUNCHES["count"]
         for _ in range(2):
-            cache.set_length(prompt)
+            self._rewind()
             self.step()
         comm.sync()
         self.allreduce_bytes_per_step = (model.comm_bytes() - b0) // 2
@@ -572,12 +617,12 @@ class _DecodeRunner:
         graph, err = None, None
         try:
             side = torch.cuda.Stream(comm.device)
-            cache.set_length(prompt)
+            self._rewind()
             side.wait_stream(torch.cuda.current_stream(comm.device))
             with torch.cuda.stream(side):
                 self.step()
             torch.cuda.current_stream(comm.device).wait_stream(side)
-            cache.set_length(prompt)
+            self._rewind()
             comm.sync()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -590,10 +635,23 @@ class _DecodeRunner:
         if errs:
             self.graph_note = f"capture failed on rank(s) {sorted(errs)}: {errs[min(errs)]}"
             return
-        cache.set_length(prompt)
+        self._rewind()
         graph.replay()
         comm.sync()
         self.graph = graph
+
+    def _rewind(self) -> None:
+        """The cache as the prefill leaves it: every row at the prompt, or at its own length."""
+        if self.lens:
+            self.cache.set_lengths(self.lens)
+        else:
+            self.cache.set_length(self.prompt)
+
+    def _last_rows(self, y):
+        """``[B, 1, H]``: the prefill output at every row's last real token."""
+        if self.last is None:
+            return y[:, -1:]
+        return y[self.rows, self.last][:, None]
 
     def step(self) -> None:
         y = self.model(self.x, kv_cache=self.cache)
@@ -603,9 +661,9 @@ class _DecodeRunner:
         """N steps from the state the prefill left (cache length = prompt)."""
         import torch
 
-        self.x.copy_(prefill_out[:, -1:])
+        self.x.copy_(self._last_rows(prefill_out))
         # a replayed prefill advanced the device length only: bring the host mirror along
-        self.cache.set_length(self.prompt)
+        self._rewind()
         run = self.graph.replay if self.graph is not None else self.step
         self.comm.sync()
         if self.gpu:
@@ -631,6 +689,8 @@ class _DecodeRunner:
         B = self.x.shape[0]
         # step i reads the K and V of positions [0, prompt + i] in every layer
         kv_mean = self.kv_per_key * (self.prompt + (self.n + 1) / 2.0)
+        if self.lens:                           # each row from its own length: the sum over rows
+            kv_mean = self.kv_per_key // B * sum(v + (self.n + 1) / 2.0 for v in self.lens)
         weights = self.model.get_memory_footprint()
         w8 = self.model.decode_weight_dtype == "fp8"
         w4 = self.model.decode_weight_dtype == "mxfp4"
@@ -663,6 +723,8 @@ class _DecodeRunner:
             "weight_dtype": self.model.decode_weight_dtype,
             "kv_dtype": self.cache.kv_dtype,
         }
+        if self.lens:
+            rec["prompt_lengths"] = list(self.lens)
         if w8:
             # the e4m3 bytes and row scales of every linear (+ the LayerNorm parameters): what a
             # step streams; weight_bytes_per_rank stays the resident bf16 footprint

@@ -6,6 +6,13 @@
 // cached, shared by the batch (and by every layer). Every kernel here reads it from device
 // memory, so a step captured in a HIP graph replays for successive positions.
 //
+// Per-sequence lengths (the *_seq entry points): `length` is int32[B] and row b of every kernel
+// uses length[b]; length[b] < 0 marks a slot that holds no sequence (nothing appended, its split
+// workgroups exit before any load or store, the combine writes zeros to its output row). The
+// kernels are the same templates with PerSeq = true: the work of a workgroup for a given
+// (b, h, c, L) is that of the shared-length kernel, only where L comes from differs. The
+// shared-length forms (PerSeq = false) are instantiations of their own, compiled as before.
+//
 //   bf16 cache  rows of D bf16 (2 D bytes).
 //   FP8 cache   rows of D e4m3fn bytes and k_scale / v_scale [B, H, L_max] fp32: one scale per
 //               cached row, row ~= float(code) * scale (D + 4 bytes a row). A row is quantised
@@ -95,9 +102,10 @@ struct KvAppendArgs {
   int B, T, H, D, L_max;
 };
 
-// one 16-byte vector per thread step: (b, t, k|v, h, piece)
+// one 16-byte vector per thread step: (b, t, k|v, h, piece). PerSeq: length[b], not *length
+template <bool PerSeq>
 __global__ __launch_bounds__(256) void kv_append_kernel(KvAppendArgs a) {
-  const int len = *a.length;
+  [[maybe_unused]] const int len0 = PerSeq ? 0 : *a.length;
   const int vpr = a.D / 8;                                  // vectors per head row
   const int64_t per_tok = 2LL * a.H * vpr;
   const int64_t total = static_cast<int64_t>(a.B) * a.T * per_tok;
@@ -110,6 +118,9 @@ __global__ __launch_bounds__(256) void kv_append_kernel(KvAppendArgs a) {
     const int kv = r / (a.H * vpr);
     const int hp = r - kv * a.H * vpr;                      // h * vpr + piece
     const int h = hp / vpr, piece = hp - h * vpr;
+    int len;
+    if constexpr (PerSeq) len = a.length[b];
+    else len = len0;
     const int64_t pos = static_cast<int64_t>(len) + t;
     if (len < 0 || pos >= a.L_max) continue;                // device-side guard: never past the cache
     const u16x8 val = *reinterpret_cast<const u16x8*>(
@@ -134,10 +145,10 @@ struct KvAppend8Args {
 
 // a row (b, t, k|v, h) of D bf16 per group of D / 8 lanes; uniform trip count over the grid, so
 // every lane of a group is active in the shuffles
-template <int D>
+template <int D, bool PerSeq>
 __global__ __launch_bounds__(256) void kv_append_fp8_kernel(KvAppend8Args a) {
   constexpr int LG = D / 8;                                 // lanes per row
-  const int len = *a.length;
+  [[maybe_unused]] const int len0 = PerSeq ? 0 : *a.length;
   const int64_t rows = static_cast<int64_t>(a.B) * a.T * 2 * a.H;
   const int64_t step = static_cast<int64_t>(gridDim.x) * blockDim.x / LG;
   const int piece = threadIdx.x % LG;
@@ -162,6 +173,9 @@ __global__ __launch_bounds__(256) void kv_append_fp8_kernel(KvAppend8Args a) {
     for (int off = 1; off < LG; off <<= 1) amax = __builtin_fmaxf(amax, __shfl_xor(amax, off, 64));
     float inv, scale;
     row_scale(amax, inv, scale);
+    int len;
+    if constexpr (PerSeq) len = a.length[b];                // b < B also for a dead lane (rr = 0)
+    else len = len0;
     const int64_t pos = static_cast<int64_t>(len) + t;
     if (!live || len < 0 || pos >= a.L_max) continue;       // device-side guard: never past the cache
     const int64_t dst = (static_cast<int64_t>(b) * a.H + h) * a.L_max + pos;
@@ -186,11 +200,19 @@ struct DecodeArgs {
   float scale_log2;
 };
 
-// keys the step attends (and whether the new token has a cache slot): uniform, from device memory
-__device__ __forceinline__ int decode_keys(const DecodeArgs& a, int& len, bool& room) {
-  len = *a.length;
-  if (len < 0) len = 0;
-  room = len < a.L_max;
+// keys the step attends (and whether the new token has a cache slot): uniform, from device
+// memory. PerSeq: row b's own length; a negative one is an empty slot, 0 keys, len stays < 0
+template <bool PerSeq>
+__device__ __forceinline__ int decode_keys(const DecodeArgs& a, int b, int& len, bool& room) {
+  if constexpr (PerSeq) {
+    len = a.length[b];
+    room = len < a.L_max;
+    if (len < 0) return 0;
+  } else {
+    len = *a.length;
+    if (len < 0) len = 0;
+    room = len < a.L_max;
+  }
   return room ? len + 1 : a.L_max;
 }
 
@@ -239,7 +261,7 @@ __device__ __forceinline__ void quant_row16(const uint16_t* p, u32x4& code, floa
                             f[4 * i + 3] * inv);
 }
 
-template <int D, typename Fmt>
+template <int D, typename Fmt, bool PerSeq>
 __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeArgs a) {
   using Elem = typename Fmt::Elem;
   using Frag = typename Fmt::Frag;
@@ -252,9 +274,10 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
   const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   int len;
   bool room;
-  const int L = decode_keys(a, len, room);
+  const int L = decode_keys<PerSeq>(a, b, len, room);
   const int k0 = c * a.chunk;
-  if (k0 >= L) return;                       // dead chunk: no K / V read, no partial written
+  if (k0 >= L) return;                       // dead chunk (every chunk of an empty slot): no K / V
+                                             // read, no partial written
   const int k1 = min(k0 + a.chunk, L);
   const int tid = threadIdx.x, sub = tid % LPK, slot = tid / LPK;
   // position whose K / V come from qkv (and are stored to the cache here); -1: none
@@ -434,12 +457,18 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
 }
 
 // grid (H, B), D threads: thread d owns output column d of head h
-template <int D>
+template <int D, bool PerSeq>
 __global__ __launch_bounds__(D) void attn_decode_combine_kernel(DecodeArgs a) {
   const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
   int len;
   bool room;
-  const int L = decode_keys(a, len, room);
+  const int L = decode_keys<PerSeq>(a, b, len, room);
+  if constexpr (PerSeq) {
+    if (len < 0) {                                   // an empty slot has no partials: zeros
+      a.out[static_cast<int64_t>(b) * a.ldo + h * D + d] = 0;
+      return;
+    }
+  }
   const int live = min((L + a.chunk - 1) / a.chunk, a.n_chunks);
   const float* p = a.ws + (static_cast<int64_t>(b) * a.H + h) * a.n_chunks * (D + 2);
   float mx = kDecNegBig;
@@ -466,19 +495,23 @@ bool qkv_cache_ok(const void* qkv, int64_t ld, const void* k_cache, const void* 
   return !(mis(qkv, 16) || mis(k_cache, 16) || mis(v_cache, 16));
 }
 
+// the per-sequence `length`: int32[B], read as length[b]
+bool seq_length_ok(const void* length) { return length && !mis(length, 4); }
+
 // the FP8 cache's scale planes
 bool scales_ok(const void* k_scale, const void* v_scale) {
   return k_scale && v_scale && !mis(k_scale, 4) && !mis(v_scale, 4);
 }
 
 // validation and the split + combine launches of both decode entry points
-template <typename Fmt>
+template <typename Fmt, bool PerSeq>
 int decode_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, void* k_scale,
                   void* v_scale, const void* length, void* ws, void* out, int64_t ldo, int B,
                   int H, int D, int L_max, int len_bound, int chunk, int fused, float scale,
                   hipStream_t stream) {
   if (B <= 0 || H <= 0) return hipSuccess;
   if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
+  if (PerSeq && !seq_length_ok(length)) return hipErrorInvalidValue;
   if (chunk <= 0 || len_bound <= 0 || !ws || ldo < H * D) return hipErrorInvalidValue;
   if (!k_cache || !v_cache || !out) return hipErrorInvalidValue;
   if (Fmt::kScaled && !scales_ok(k_scale, v_scale)) return hipErrorInvalidValue;
@@ -492,12 +525,52 @@ int decode_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, voi
                n_chunks, fused ? 1 : 0, scale * 1.4426950408889634f};
   const dim3 gs(n_chunks, H, B), gc(H, B);
   if (D == 64) {
-    hipLaunchKernelGGL((attn_decode_split_kernel<64, Fmt>), gs, dim3(kDecThreads), 0, stream, a);
-    hipLaunchKernelGGL(attn_decode_combine_kernel<64>, gc, dim3(64), 0, stream, a);
+    hipLaunchKernelGGL((attn_decode_split_kernel<64, Fmt, PerSeq>), gs, dim3(kDecThreads), 0,
+                       stream, a);
+    hipLaunchKernelGGL((attn_decode_combine_kernel<64, PerSeq>), gc, dim3(64), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((attn_decode_split_kernel<128, Fmt>), gs, dim3(kDecThreads), 0, stream, a);
-    hipLaunchKernelGGL(attn_decode_combine_kernel<128>, gc, dim3(128), 0, stream, a);
+    hipLaunchKernelGGL((attn_decode_split_kernel<128, Fmt, PerSeq>), gs, dim3(kDecThreads), 0,
+                       stream, a);
+    hipLaunchKernelGGL((attn_decode_combine_kernel<128, PerSeq>), gc, dim3(128), 0, stream, a);
   }
+  return hipGetLastError();
+}
+
+// validation and the launch of both bf16 append entry points
+template <bool PerSeq>
+int append_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, const void* length,
+                  int B, int T, int H, int D, int L_max, hipStream_t stream) {
+  if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
+  if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
+  if (PerSeq && !seq_length_ok(length)) return hipErrorInvalidValue;
+  KvAppendArgs a{static_cast<const uint16_t*>(qkv), static_cast<uint16_t*>(k_cache),
+                 static_cast<uint16_t*>(v_cache), static_cast<const int*>(length), ld, B, T, H, D,
+                 L_max};
+  const int64_t vecs = static_cast<int64_t>(B) * T * 2 * H * (D / 8);
+  hipLaunchKernelGGL(kv_append_kernel<PerSeq>, dim3(stream_grid(vecs, 256)), dim3(256), 0, stream,
+                     a);
+  return hipGetLastError();
+}
+
+// the same for both FP8 append entry points
+template <bool PerSeq>
+int append_fp8_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, void* k_scale,
+                      void* v_scale, const void* length, int B, int T, int H, int D, int L_max,
+                      hipStream_t stream) {
+  if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
+  if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
+  if (PerSeq && !seq_length_ok(length)) return hipErrorInvalidValue;
+  if (!k_cache || !v_cache || !scales_ok(k_scale, v_scale)) return hipErrorInvalidValue;
+  KvAppend8Args a{static_cast<const uint16_t*>(qkv), static_cast<uint8_t*>(k_cache),
+                  static_cast<uint8_t*>(v_cache), static_cast<float*>(k_scale),
+                  static_cast<float*>(v_scale), static_cast<const int*>(length), ld, B, T, H,
+                  L_max};
+  const int64_t lanes = static_cast<int64_t>(B) * T * 2 * H * (D / 8);
+  const dim3 grid(stream_grid(lanes, 256));
+  if (D == 64)
+    hipLaunchKernelGGL((kv_append_fp8_kernel<64, PerSeq>), grid, dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL((kv_append_fp8_kernel<128, PerSeq>), grid, dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -513,14 +586,15 @@ using namespace dlbb;
 DLBB_API int dlbb_kv_append(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
                             const void* length, int B, int T, int H, int D, int L_max,
                             hipStream_t stream) {
-  if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
-  if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
-  KvAppendArgs a{static_cast<const uint16_t*>(qkv), static_cast<uint16_t*>(k_cache),
-                 static_cast<uint16_t*>(v_cache), static_cast<const int*>(length), ld, B, T, H, D,
-                 L_max};
-  const int64_t vecs = static_cast<int64_t>(B) * T * 2 * H * (D / 8);
-  hipLaunchKernelGGL(kv_append_kernel, dim3(stream_grid(vecs, 256)), dim3(256), 0, stream, a);
-  return hipGetLastError();
+  return append_launch<false>(qkv, ld, k_cache, v_cache, length, B, T, H, D, L_max, stream);
+}
+
+// Per-sequence lengths: length is device int32[B]; row b's tokens go to positions [length[b],
+// length[b] + T), nothing is written for a row with length[b] < 0.
+DLBB_API int dlbb_kv_append_seq(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                const void* length, int B, int T, int H, int D, int L_max,
+                                hipStream_t stream) {
+  return append_launch<true>(qkv, ld, k_cache, v_cache, length, B, T, H, D, L_max, stream);
 }
 
 // The same for the FP8 cache: k_cache / v_cache [B, H, L_max, D] e4m3fn contiguous, k_scale /
@@ -530,20 +604,16 @@ DLBB_API int dlbb_kv_append(const void* qkv, int64_t ld, void* k_cache, void* v_
 DLBB_API int dlbb_kv_append_fp8(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
                                 void* k_scale, void* v_scale, const void* length, int B, int T,
                                 int H, int D, int L_max, hipStream_t stream) {
-  if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
-  if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
-  if (!k_cache || !v_cache || !scales_ok(k_scale, v_scale)) return hipErrorInvalidValue;
-  KvAppend8Args a{static_cast<const uint16_t*>(qkv), static_cast<uint8_t*>(k_cache),
-                  static_cast<uint8_t*>(v_cache), static_cast<float*>(k_scale),
-                  static_cast<float*>(v_scale), static_cast<const int*>(length), ld, B, T, H,
-                  L_max};
-  const int64_t lanes = static_cast<int64_t>(B) * T * 2 * H * (D / 8);
-  const dim3 grid(stream_grid(lanes, 256));
-  if (D == 64)
-    hipLaunchKernelGGL(kv_append_fp8_kernel<64>, grid, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(kv_append_fp8_kernel<128>, grid, dim3(256), 0, stream, a);
-  return hipGetLastError();
+  return append_fp8_launch<false>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, B, T, H, D,
+                                  L_max, stream);
+}
+
+// The FP8 append with per-sequence lengths (dlbb_kv_append_seq's contract).
+DLBB_API int dlbb_kv_append_fp8_seq(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                    void* k_scale, void* v_scale, const void* length, int B,
+                                    int T, int H, int D, int L_max, hipStream_t stream) {
+  return append_fp8_launch<true>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, B, T, H, D,
+                                 L_max, stream);
 }
 
 // One decode step of attention: qkv [B, 1, 3, H, D] (batch row stride ld), the bf16 cache as
@@ -555,7 +625,7 @@ DLBB_API int dlbb_attn_decode(const void* qkv, int64_t ld, void* k_cache, void* 
                               const void* length, void* ws, void* out, int64_t ldo, int B, int H,
                               int D, int L_max, int len_bound, int chunk, int fused, float scale,
                               hipStream_t stream) {
-  return decode_launch<KvBf16>(qkv, ld, k_cache, v_cache, nullptr, nullptr, length, ws, out, ldo,
+  return decode_launch<KvBf16, false>(qkv, ld, k_cache, v_cache, nullptr, nullptr, length, ws, out, ldo,
                                B, H, D, L_max, len_bound, chunk, fused, scale, stream);
 }
 
@@ -566,6 +636,28 @@ DLBB_API int dlbb_attn_decode_fp8(const void* qkv, int64_t ld, void* k_cache, vo
                                   void* out, int64_t ldo, int B, int H, int D, int L_max,
                                   int len_bound, int chunk, int fused, float scale,
                                   hipStream_t stream) {
-  return decode_launch<KvE4m3>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, ws, out, ldo,
+  return decode_launch<KvE4m3, false>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, ws, out, ldo,
                                B, H, D, L_max, len_bound, chunk, fused, scale, stream);
+}
+
+// The decode step with per-sequence lengths: length is device int32[B], row b attends over
+// length[b] + 1 keys (L_max keys and no store when length[b] >= L_max); a row with length[b] < 0
+// is an empty slot: nothing read or stored, its output row is zeros. len_bound is the host's upper
+// bound of max_b length[b] + 1.
+DLBB_API int dlbb_attn_decode_seq(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                  const void* length, void* ws, void* out, int64_t ldo, int B,
+                                  int H, int D, int L_max, int len_bound, int chunk, int fused,
+                                  float scale, hipStream_t stream) {
+  return decode_launch<KvBf16, true>(qkv, ld, k_cache, v_cache, nullptr, nullptr, length, ws, out,
+                                     ldo, B, H, D, L_max, len_bound, chunk, fused, scale, stream);
+}
+
+// The same over the FP8 cache.
+DLBB_API int dlbb_attn_decode_fp8_seq(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                      void* k_scale, void* v_scale, const void* length, void* ws,
+                                      void* out, int64_t ldo, int B, int H, int D, int L_max,
+                                      int len_bound, int chunk, int fused, float scale,
+                                      hipStream_t stream) {
+  return decode_launch<KvE4m3, true>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, ws, out,
+                                     ldo, B, H, D, L_max, len_bound, chunk, fused, scale, stream);
 }

@@ -133,7 +133,9 @@ class TransformerBlock(nn.Module):
         (the token's K / V stored at ``cache.length``, attention over ``length + 1`` keys).
         ``flash`` runs our kernels (``ops.causal_attention`` + ``ops.kv_append``,
         ``ops.decode_attention``); ``sdpa`` and ``kernels="torch"`` the torch forms at the host
-        position. The cache is advanced by the model, not here."""
+        position. The cache is advanced by the model, not here. A per-sequence cache hands its
+        ``int32[B]`` ``length`` and its list of host positions through the same calls: the ops
+        dispatch on ``length.numel()``."""
         from ..ops import decode as dec
 
         k, v = cache.k[layer], cache.v[layer]
@@ -146,11 +148,16 @@ class TransformerBlock(nn.Module):
                                             len_bound=cache.len_bound,
                                             workspace=cache.workspace, pos=cache.pos,
                                             k_scale=ks, v_scale=vs)
+            if cache.per_sequence:
+                return dec.torch_decode_attention_seq(qkv, heads, k, v, cache.pos, ks, vs)
             return dec.torch_decode_attention(qkv, heads, k, v, cache.pos, ks, vs)
         if hip:
             ops.kv_append(qkv, heads, k, v, cache.length, pos=cache.pos, k_scale=ks, v_scale=vs)
             return ops.causal_attention(qkv, heads)
-        dec.torch_kv_append(qkv, heads, k, v, cache.pos, ks, vs)
+        if cache.per_sequence:
+            dec.torch_kv_append_seq(qkv, heads, k, v, cache.pos, ks, vs)
+        else:
+            dec.torch_kv_append(qkv, heads, k, v, cache.pos, ks, vs)
         return self._attn(qkv)
 
     def forward(self, y1: torch.Tensor, h: torch.Tensor):
@@ -229,14 +236,15 @@ class LLM(nn.Module):
                 return car
         return None
 
-    def new_kv_cache(self, batch: int, max_len: int):
+    def new_kv_cache(self, batch: int, max_len: int, per_sequence: bool = False):
         """A :class:`ops.KVCache` for this rank's ``num_heads / P`` local heads, ``max_len``
         positions. ``attention="slice"`` (the stateless stub) gets one with no K / V storage:
         decode still runs, and measures the GEMMs and the ``[B, 1, H]`` all-reduces alone.
         With ``decode_weight_dtype="fp8"`` on the HIP path the batch is the M of the W8 skinny
         GEMM (``"mxfp4"``: of the W4 one): more than 16 rows raise here, not in the middle of a
         step. ``kv_cache_dtype`` picks the cache's storage (``"fp8"``: e4m3 codes + one fp32
-        scale per row)."""
+        scale per row). ``per_sequence=True``: one length per batch row (``ops.decode``), for a
+        batch whose sequences differ in length; see :meth:`forward`."""
         if (self.decode_weight_dtype != "bf16" and batch > 16 and self.kernels != "torch"
                 and self.comm.device.type == "cuda" and not ops._lib.force_torch()):
             which = "W8" if self.decode_weight_dtype == "fp8" else "W4"
@@ -246,7 +254,8 @@ class LLM(nn.Module):
         heads = self.num_heads // self.world_size
         layers = 0 if self.attention == "slice" else self.num_layers
         return ops.KVCache(layers, batch, heads, self.hidden_size // self.num_heads, max_len,
-                           self.comm.device, kv_dtype=self.kv_cache_dtype)
+                           self.comm.device, kv_dtype=self.kv_cache_dtype,
+                           per_sequence=per_sequence)
 
     def _micro_batch(self, x: torch.Tensor, slot: int = 0, stream=None, cache=None):
         """One micro-batch's forward as a generator over its all-reduces (see
@@ -269,13 +278,24 @@ class LLM(nn.Module):
             return 1
         return n
 
-    def forward(self, x: torch.Tensor, kv_cache=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, kv_cache=None, prompt_lens=None) -> torch.Tensor:
         """With ``kv_cache`` (:meth:`new_kv_cache`) and ``x [B, T, H]`` every block appends its
         K / V: ``T > 1`` on an empty cache is the prefill, ``T == 1`` a decode step over the
         cached tokens; ``T > 1`` on a non-empty cache raises ``ValueError`` (no chunked
         prefill). After the final LayerNorm the cache advances by ``T`` (a device add on the
         current stream, captured with the step). With a cache the forward runs as ONE
         micro-batch: ``overlap_chunks`` is ignored there.
+
+        With a per-sequence cache (``new_kv_cache(..., per_sequence=True)``) ``T > 1`` is the
+        prefill of a RIGHT-PADDED batch: every live row must be empty, all ``T`` rows are appended
+        from position 0, the causal attention is the usual one (causality keeps every real
+        token's output independent of the padding behind it) and the cache ends at
+        ``set_lengths(prompt_lens)`` (default: ``T`` for every live row). The padding rows left
+        in the cache lie at or past ``length[b]``: never read, overwritten as the sequence grows.
+        ``T == 1`` is a decode step of the live rows, then ``advance(1)``; an empty slot's
+        output row is not meaningful. A ``prompt_lens`` entry outside ``[1, T]`` raises before
+        any launch, and so does ``prompt_lens`` on a shared-length cache. One slot of such a
+        cache is refilled through ``kv_cache.slot(b)``, a batch-1 shared-length cache.
 
         Without a cache — plain: one pass, each all-reduce inline. Overlapped (``overlap_chunks`` = n > 1): the
         batch is split into n micro-batches run round-robin, each advancing to its next
@@ -288,7 +308,16 @@ class LLM(nn.Module):
             T = x.shape[1]
             if x.shape[0] != kv_cache.batch:
                 raise ValueError(f"batch {x.shape[0]} != the cache's {kv_cache.batch}")
-            if T > 1 and kv_cache.pos != 0:
+            if prompt_lens is not None:
+                if not kv_cache.per_sequence:
+                    raise ValueError("prompt_lens needs a per_sequence=True KV cache")
+                prompt_lens = [int(v) for v in prompt_lens]
+                if T == 1 or len(prompt_lens) != x.shape[0] \
+                        or any(not 1 <= v <= T for v in prompt_lens):
+                    raise ValueError(f"prompt_lens {prompt_lens}: need {x.shape[0]} values in "
+                                     f"[1, {T}] with a prefill of T > 1 tokens")
+            if T > 1 and (any(p > 0 for p in kv_cache.pos) if kv_cache.per_sequence
+                          else kv_cache.pos != 0):
                 raise ValueError(f"prefill of {T} tokens on a cache holding {kv_cache.pos}: "
                                  "chunked prefill is not supported")
             kv_cache.check_room(T)
@@ -300,7 +329,12 @@ class LLM(nn.Module):
                     next(gen)
             except StopIteration as e:
                 if kv_cache is not None:
-                    kv_cache.advance(x.shape[1])
+                    if prompt_lens is not None:
+                        # empty slots stay empty: their rows of the padded batch are not kept
+                        kv_cache.set_lengths([n if p >= 0 else -1
+                                              for n, p in zip(prompt_lens, kv_cache.pos)])
+                    else:
+                        kv_cache.advance(x.shape[1])
                 return e.value
         stream = None
         cur = torch.cuda.current_stream(x.device) if x.is_cuda else None

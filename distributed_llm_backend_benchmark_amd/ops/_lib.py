@@ -168,6 +168,18 @@ _SIGS = {
     "dlbb_attn_decode_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    # per-sequence lengths (length = int32[B]): the signatures of the four above
+    "dlbb_kv_append_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                   c_int, c_int, c_int, c_void_p]),
+    "dlbb_attn_decode_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, c_float, c_void_p]),
+    "dlbb_kv_append_fp8_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dlbb_attn_decode_fp8_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                         c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                         c_void_p]),
     "dlbb_rccl_unique_id_bytes": (c_int, []),
     "dlbb_rccl_get_unique_id": (c_int, [c_void_p]),
     "dlbb_rccl_init": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

@@ -44,12 +44,33 @@ FP8 cache (opt-in, ``KVCache(kv_dtype="fp8")``; the same file's ``KvE4m3`` kerne
 head dim 64 / 128 and contiguous bf16 ``qkv``; the torch forms otherwise (the append quantises
 with ``fp8._quantize_torch``, the decode dequantises ``cache[:, :, :pos + 1]`` to fp32 and runs
 SDPA).
+
+Per-sequence lengths (opt-in, ``KVCache(per_sequence=True)``; the ``*_seq`` entry points, the same
+kernel templates with ``length[b]`` in place of ``*length``). The contract:
+
+* ``length`` is a device ``int32[B]``: row ``b`` of the batch holds ``length[b]`` cached tokens.
+  :func:`kv_append` and :func:`decode_attention` dispatch on ``length.numel()``: 1 is the shared
+  length above, ``B`` the per-sequence path, anything else raises ``ValueError`` (so a batch of
+  one always takes the shared-length kernels).
+* ``length[b] < 0`` marks an EMPTY slot: the append writes nothing for it, its split workgroups
+  exit before any load or store and its output row is zeros. (The shared-length kernels clamp a
+  negative length to 0; that stays.)
+* The device guards are per row: ``length[b] >= L_max`` attends over ``L_max`` keys and stores
+  nothing, append positions ``>= L_max`` are dropped.
+* ``len_bound`` is the host's upper bound of ``max_b length[b] + 1``; ``pos`` may be a sequence of
+  ``B`` host positions (overflow checks, and the torch path).
+* For a given ``(b, h, chunk, L)`` a workgroup does exactly what the shared-length kernel does,
+  so row ``b`` of a ragged launch has the bits of a batch-1 shared-length launch at
+  ``length[b]``.
+* Torch forms: a per-row index copy for the append and, for the decode, the shared-length torch
+  form on each row's batch-1 slice at its host position (bit-identical to it; a single masked
+  SDPA is not); empty slots give zero rows.
 """
 
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import List, Optional, Sequence, Union
 
 import torch
 import torch.nn.functional as F
@@ -84,15 +105,24 @@ class KVCache:
     workspace. ``num_layers = 0`` holds no K / V (the stateless ``attention="slice"`` stub):
     only the position bookkeeping. ``kv_dtype="fp8"``: ``k`` / ``v`` hold e4m3 codes and
     ``k_scale`` / ``v_scale`` one fp32 scale per cached row (module docstring); with ``"bf16"``
-    the two scale lists hold ``None`` per layer."""
+    the two scale lists hold ``None`` per layer.
+
+    ``per_sequence=True``: ``length`` is ``int32[B]`` and ``pos`` a list of ``B`` host mirrors, one
+    per batch row; a negative entry is an empty slot (module docstring). :meth:`set_lengths`,
+    :meth:`retire`, :meth:`slot` and :meth:`live_bytes` belong to that form; :meth:`advance` moves
+    the live rows only."""
 
     def __init__(self, num_layers: int, batch: int, n_head_local: int, head_dim: int,
-                 max_len: int, device, dtype=torch.bfloat16, kv_dtype: str = "bf16"):
+                 max_len: int, device, dtype=torch.bfloat16, kv_dtype: str = "bf16",
+                 per_sequence: bool = False):
         if max_len < 1 or batch < 1:
             raise ValueError(f"KVCache needs batch >= 1 and max_len >= 1, got {batch}, {max_len}")
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"KVCache kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
         self.kv_dtype = kv_dtype
+        self.per_sequence = bool(per_sequence)
+        self._parent, self._row = None, 0       # set on a slot view (:meth:`slot`)
+        self._staged = None                     # (values, device tensor) of :meth:`set_lengths`
         fp8 = kv_dtype == "fp8"
         if fp8:
             dtype = E4M3
@@ -110,8 +140,10 @@ class KVCache:
         self.v_scale: List[Optional[torch.Tensor]] = [
             torch.ones(shape[:3], dtype=torch.float32, device=self.device) if fp8 else None
             for _ in range(self.num_layers)]
-        self.length = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.pos = 0                    # host mirror of `length`: bounds checks only
+        self.length = torch.zeros(self.batch if self.per_sequence else 1, dtype=torch.int32,
+                                  device=self.device)
+        # host mirror of `length`: bounds checks only (a list of B with per_sequence)
+        self._pos: Union[int, List[int]] = [0] * self.batch if self.per_sequence else 0
         # host upper bound of length + 1 for the split grid (None = max_len); a runner that
         # replays one captured step sets the final position here before the capture
         self.len_bound: Optional[int] = None
@@ -120,23 +152,101 @@ class KVCache:
                                       dtype=torch.float32, device=self.device)
                           if self.num_layers else None)
 
+    @property
+    def pos(self):
+        return self._pos
+
+    @pos.setter
+    def pos(self, value) -> None:
+        self._pos = value
+        if self._parent is not None:            # a slot view mirrors its position back
+            self._parent._pos[self._row] = int(value)
+
     def set_length(self, n: int) -> None:
-        """Set the device length and the host mirror (0 = empty the cache)."""
+        """Set the device length and the host mirror (0 = empty the cache); with
+        ``per_sequence`` every row gets ``n``."""
         if not 0 <= n <= self.max_len:
             raise ValueError(f"KVCache length {n} outside [0, {self.max_len}]")
         self.length.fill_(int(n))
-        self.pos = int(n)
+        self.pos = [int(n)] * self.batch if self.per_sequence else int(n)
+
+    def _need_per_sequence(self, what: str) -> None:
+        if not self.per_sequence:
+            raise ValueError(f"KVCache.{what} needs a per_sequence=True cache")
+
+    def set_lengths(self, lengths: Sequence[int]) -> None:
+        """Set every row's device length and host mirror; a negative entry empties the slot.
+        The values are staged in a device tensor that the same values reuse, so a call repeated
+        under HIP-graph capture (after an eager call with these values) is a device copy."""
+        self._need_per_sequence("set_lengths")
+        vals = [int(v) for v in lengths]
+        if len(vals) != self.batch or any(v > self.max_len for v in vals):
+            raise ValueError(f"KVCache lengths {vals}: need {self.batch} values <= {self.max_len}")
+        vals = [max(v, -1) for v in vals]
+        if self._staged is None or self._staged[0] != vals:
+            self._staged = (vals, torch.tensor(vals, dtype=torch.int32, device=self.device))
+        self.length.copy_(self._staged[1])
+        self.pos = vals
+
+    def retire(self, b: int) -> None:
+        """Row ``b`` holds no sequence any more: ``length[b] = -1``."""
+        self._need_per_sequence("retire")
+        self.length[b:b + 1].fill_(-1)
+        self._pos[b] = -1
 
     def check_room(self, t: int) -> None:
-        if self.pos + t > self.max_len:
-            raise ValueError(f"KVCache overflow: position {self.pos} + {t} tokens > max_len "
+        top = max(self._pos) if self.per_sequence else self._pos     # the longest live row
+        if top + t > self.max_len:
+            raise ValueError(f"KVCache overflow: position {top} + {t} tokens > max_len "
                              f"{self.max_len}")
 
     def advance(self, t: int) -> None:
-        """``length += t``: a device add on the current stream (captured with the step)."""
+        """``length += t``: a device add on the current stream (captured with the step). With
+        ``per_sequence`` the add is ``(length >= 0) * t``: empty slots stay empty."""
         self.check_room(t)
+        if self.per_sequence:
+            self.length.add_((self.length >= 0).to(torch.int32) * int(t))
+            self.pos = [p + int(t) if p >= 0 else p for p in self._pos]
+            return
         self.length.add_(int(t))
         self.pos += int(t)
+
+    def slot(self, b: int) -> "KVCache":
+        """A batch-1 shared-length :class:`KVCache` over row ``b``: views of its K / V, scales
+        and ``length[b:b + 1]`` (``[B, H, L_max, D]`` is contiguous in ``b``) and the parent's
+        workspace, so a prompt can be prefilled into one slot while the other rows keep their
+        contents. Its position is mirrored back to the parent. A retired row reads -1: claim it
+        with ``set_length(0)`` first."""
+        self._need_per_sequence("slot")
+        if not 0 <= b < self.batch:
+            raise ValueError(f"KVCache.slot({b}): batch is {self.batch}")
+        s = object.__new__(KVCache)
+        s.kv_dtype, s.per_sequence = self.kv_dtype, False
+        s.num_layers, s.batch = self.num_layers, 1
+        s.n_head, s.head_dim, s.max_len = self.n_head, self.head_dim, self.max_len
+        s.device = self.device
+        s.k = [t[b:b + 1] for t in self.k]
+        s.v = [t[b:b + 1] for t in self.v]
+        s.k_scale = [None if t is None else t[b:b + 1] for t in self.k_scale]
+        s.v_scale = [None if t is None else t[b:b + 1] for t in self.v_scale]
+        s.length = self.length[b:b + 1]
+        s._parent, s._row, s._staged = self, int(b), None
+        s._pos = self._pos[b]
+        s.len_bound = None
+        s.workspace = self.workspace
+        return s
+
+    def _position_bytes(self) -> int:
+        """K, V and scale bytes of one cached position of one batch row, over every layer."""
+        row = self.head_dim + 4 if self.kv_dtype == "fp8" else 2 * self.head_dim
+        return self.num_layers * self.n_head * row * 2
+
+    def live_bytes(self) -> int:
+        """K, V and scale bytes of the live rows only: the cached positions below each row's
+        length (by the host mirrors), over every layer."""
+        held = (sum(p for p in self._pos if p > 0) if self.per_sequence
+                else self.batch * max(self._pos, 0))
+        return held * self._position_bytes()
 
     @property
     def nbytes(self) -> int:
@@ -221,41 +331,114 @@ def torch_decode_attention(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale
     return o.transpose(1, 2).reshape(B, 1, C3 // 3)
 
 
+def _per_sequence(length: torch.Tensor, batch: int, what: str) -> bool:
+    """The dispatch on ``length.numel()``: 1 = the shared length, ``B`` = one per batch row."""
+    n = length.numel()
+    if n == 1:
+        return False
+    if n != batch:
+        raise ValueError(f"{what}: length has {n} elements, need 1 (shared) or the batch "
+                         f"size {batch} (per sequence)")
+    return True
+
+
+def _host_positions(length: torch.Tensor, pos) -> List[int]:
+    """The ``B`` host positions of the per-sequence path (from the device when ``pos`` is None)."""
+    p = length.tolist() if pos is None else [int(v) for v in pos]
+    if len(p) != length.numel():
+        raise ValueError(f"pos has {len(p)} entries for a length of {length.numel()}")
+    return p
+
+
+def torch_kv_append_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int], k_scale=None,
+                        v_scale=None) -> None:
+    """Torch form of the per-sequence :func:`kv_append`: row ``b`` is copied at the host position
+    ``pos[b]``; nothing for an empty slot (``pos[b] < 0``)."""
+    for b, p in enumerate(pos):
+        if p < 0:
+            continue
+        torch_kv_append(qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p,
+                        None if k_scale is None else k_scale[b:b + 1],
+                        None if v_scale is None else v_scale[b:b + 1])
+
+
+def torch_decode_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int],
+                               k_scale=None, v_scale=None) -> torch.Tensor:
+    """Torch form of the per-sequence :func:`decode_attention` at the host positions ``pos``:
+    row ``b`` is :func:`torch_decode_attention` on the batch-1 slice of its cache at ``pos[b]``,
+    so a row has the bits of the shared-length form; empty slots give zero rows. (One SDPA over
+    the batch with a boolean key mask was tried first: with a mask torch's CPU kernel rounds the
+    scaled scores differently, and a bf16 row differed from the shared-length form by an ulp.)"""
+    B, _, C3 = qkv.shape
+    out = torch.zeros(B, 1, C3 // 3, dtype=qkv.dtype, device=qkv.device)
+    for b, p in enumerate(pos):
+        if p < 0:
+            continue
+        out[b:b + 1] = torch_decode_attention(
+            qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p,
+            None if k_scale is None else k_scale[b:b + 1],
+            None if v_scale is None else v_scale[b:b + 1])
+    return out
+
+
 def _hip_append(qkv, n_head: int, k_cache, v_cache, k_scale, v_scale, length, T: int) -> None:
-    """The HIP append of ``T`` tokens; the FP8 entry point when the cache has scales."""
+    """The HIP append of ``T`` tokens; the FP8 entry point when the cache has scales, the
+    ``_seq`` one when ``length`` has an element per batch row."""
     B, _, C3 = qkv.shape
     fp8 = k_scale is not None
     scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
-    fn = _lib.lib().dlbb_kv_append_fp8 if fp8 else _lib.lib().dlbb_kv_append
+    name = ("dlbb_kv_append_fp8" if fp8 else "dlbb_kv_append") + \
+        ("_seq" if length.numel() != 1 else "")
+    fn = getattr(_lib.lib(), name)
     check(fn(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(), *scales,
              length.data_ptr(), B, T, n_head, C3 // 3 // n_head, k_cache.shape[2],
-             _lib.stream(qkv.device)), "kv_append_fp8" if fp8 else "kv_append")
+             _lib.stream(qkv.device)), name[5:])
 
 
 def _hip_decode(qkv, n_head: int, k_cache, v_cache, k_scale, v_scale, length, workspace, out,
                 bound: int, chunk: int, fused: bool) -> None:
-    """The HIP split + combine launches; the FP8 entry point when the cache has scales."""
+    """The HIP split + combine launches; the FP8 entry point when the cache has scales, the
+    ``_seq`` one when ``length`` has an element per batch row."""
     B, _, C3 = qkv.shape
     C = C3 // 3
     D = C // n_head
     fp8 = k_scale is not None
     scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
-    fn = _lib.lib().dlbb_attn_decode_fp8 if fp8 else _lib.lib().dlbb_attn_decode
+    name = ("dlbb_attn_decode_fp8" if fp8 else "dlbb_attn_decode") + \
+        ("_seq" if length.numel() != 1 else "")
+    fn = getattr(_lib.lib(), name)
     check(fn(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(), *scales,
              length.data_ptr(), workspace.data_ptr(), out.data_ptr(), C, B, n_head, D,
              k_cache.shape[2], bound, chunk, int(fused), 1.0 / math.sqrt(D),
-             _lib.stream(qkv.device)), "attn_decode_fp8" if fp8 else "attn_decode")
+             _lib.stream(qkv.device)), name[5:])
 
 
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
-              length: torch.Tensor, pos: Optional[int] = None,
+              length: torch.Tensor, pos: Union[None, int, Sequence[int]] = None,
               k_scale: Optional[torch.Tensor] = None,
               v_scale: Optional[torch.Tensor] = None) -> None:
     """K / V rows of ``qkv [B, T, 3C]`` -> cache positions ``[length, length + T)``. ``pos``:
     the host's copy of ``length`` (raises before launch on overflow; None on the HIP path = no
     host check, the kernel drops positions past the cache). ``k_scale`` / ``v_scale``: the row
-    scales of an FP8 cache (module docstring), whose rows are quantised on the way in."""
+    scales of an FP8 cache (module docstring), whose rows are quantised on the way in. A
+    ``length`` of ``B`` elements is the per-sequence form (module docstring): row ``b`` goes to
+    ``[length[b], length[b] + T)``, ``pos`` is then a sequence of ``B`` host positions."""
     T, L_max = qkv.shape[1], k_cache.shape[2]
+    if _per_sequence(length, qkv.shape[0], "kv_append"):
+        if pos is not None:
+            pos = _host_positions(length, pos)
+            if max(pos) + T > L_max:
+                raise ValueError(f"kv_append: position {max(pos)} + {T} tokens > cache length "
+                                 f"{L_max}")
+        _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+        if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale):
+            _hip_append(qkv, n_head, k_cache, v_cache, k_scale, v_scale, length, T)
+            return
+        p = _host_positions(length, pos)
+        if max(p) + T > L_max:
+            raise ValueError(f"kv_append: position {max(p)} + {T} tokens > cache length {L_max}")
+        torch_kv_append_seq(qkv, n_head, k_cache, v_cache, p, k_scale, v_scale)
+        return
     if pos is not None and pos + T > L_max:
         raise ValueError(f"kv_append: position {pos} + {T} tokens > cache length {L_max}")
     _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
@@ -271,7 +454,7 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
 def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, length: torch.Tensor,
                      len_bound: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
-                     pos: Optional[int] = None, chunk: Optional[int] = None,
+                     pos: Union[None, int, Sequence[int]] = None, chunk: Optional[int] = None,
                      fused: Optional[bool] = None, k_scale: Optional[torch.Tensor] = None,
                      v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One decode step of causal attention: ``qkv [B, 1, 3C]`` -> ``[B, 1, C]``; the token's
@@ -285,10 +468,18 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     ``length`` for the overflow check (and the torch path). ``chunk`` / ``fused``: A/B knobs of
     ``tools/decode_bench.py`` (defaults :data:`CHUNK`, :data:`FUSED_APPEND`). ``k_scale`` /
     ``v_scale``: the row scales of an FP8 cache (module docstring): the token is stored
-    quantised and attended to in that form; the chunk default is then :data:`CHUNK_FP8`."""
+    quantised and attended to in that form; the chunk default is then :data:`CHUNK_FP8`.
+
+    A ``length`` of ``B`` elements is the per-sequence form (module docstring): row ``b`` attends
+    over ``length[b] + 1`` keys, an empty slot (``length[b] < 0``) gives a zero row; ``len_bound``
+    bounds ``max_b length[b] + 1`` and ``pos`` is a sequence of ``B`` host positions."""
     if qkv.dim() != 3 or qkv.shape[1] != 1:
         raise ValueError(f"decode_attention takes qkv [B, 1, 3C], got {tuple(qkv.shape)}")
     L_max = k_cache.shape[2]
+    seq = _per_sequence(length, qkv.shape[0], "decode_attention")
+    if seq and pos is not None:
+        host = _host_positions(length, pos)
+        pos = max(host)                          # the longest row: what the checks below bound
     if pos is not None and pos + 1 > L_max:
         raise ValueError(f"decode_attention: position {pos} + 1 > cache length {L_max}")
     fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
@@ -312,6 +503,11 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
         _hip_decode(qkv, n_head, k_cache, v_cache, k_scale, v_scale, length, workspace, out,
                     bound, chunk, fused)
         return out
+    if seq:
+        host = _host_positions(length, None) if pos is None else host
+        if max(host) + 1 > L_max:
+            raise ValueError(f"decode_attention: position {max(host)} + 1 > cache length {L_max}")
+        return torch_decode_attention_seq(qkv, n_head, k_cache, v_cache, host, k_scale, v_scale)
     p = _host_pos(length, pos)
     if p + 1 > L_max:
         raise ValueError(f"decode_attention: position {p} + 1 > cache length {L_max}")

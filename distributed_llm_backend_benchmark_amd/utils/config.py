@@ -38,6 +38,10 @@ Additions (all optional, defaults keep reference behaviour):
   holds e4m3 codes with one fp32 scale per cached row of ``head_dim`` values (``ops.decode``;
   ``run_tp --kv-cache``): ``head_dim + 4`` bytes per row instead of ``2 head_dim``. The appends
   quantise, a decode step attends to the quantised rows; the prefill attention is unchanged.
+* ``execution.prompt_lengths``: absent (default: every prompt fills ``sequence_length``) | a list
+  of ``batch_size`` ints in ``[1, sequence_length]`` — the batch is right-padded prompts of these
+  lengths and the decode steps run over a per-sequence KV cache (``ops.decode``;
+  ``run_tp --prompt-lens``). Needs ``decode_tokens`` and a real attention.
 """
 
 from __future__ import annotations
@@ -151,6 +155,17 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
     if ex["kv_cache_dtype"] not in ("bf16", "fp8"):
         raise ConfigError("execution.kv_cache_dtype must be bf16|fp8, got "
                           f"{ex['kv_cache_dtype']!r}")
+    lens = ex.get("prompt_lengths")             # no default: absent = every prompt is full
+    if lens is not None:
+        S, B = cfg["input"].get("sequence_length"), cfg["input"].get("batch_size")
+        if not isinstance(lens, (list, tuple)) or not lens or any(
+                not isinstance(v, int) or isinstance(v, bool) or v < 1 for v in lens):
+            raise ConfigError("execution.prompt_lengths must be a list of ints >= 1")
+        if isinstance(B, int) and len(lens) != B:
+            raise ConfigError(f"execution.prompt_lengths has {len(lens)} values for batch_size "
+                              f"{B}")
+        if isinstance(S, int) and max(lens) > S:
+            raise ConfigError(f"execution.prompt_lengths must lie in [1, sequence_length {S}]")
     return cfg
 
 

@@ -21,6 +21,16 @@ of exactly those code + scale bytes, ``ours_fp8_chunk<N>`` the kernel at the oth
 ``GBps`` of these candidates is over the bytes they actually read (``kv_bytes_fp8``);
 ``fp8_over_bf16`` is ``us[ours_fp8] / us[ours]``, ``fp8_vs_bf16_max_rel_diff`` the output distance
 of the two cache types on the row's inputs.
+
+``--ragged`` times the per-sequence kernels instead (same protocol, same process; rows go to
+``profiles/ragged_decode/attn_decode_ragged.jsonl``). For every shape: ``ragged`` is one decode
+step over a batch whose rows attend ``L (b + 1) / B`` keys, b = 0 .. B - 1 (spread evenly over
+``(0, L]``), through ``length = int32[B]``; ``uniform`` the shared-length step of all rows at
+``L`` (the ``ours`` of the default mode); ``uniform_seq`` the per-sequence kernel with every row at
+``L``, which isolates what ``length[b]`` costs; ``copy_live`` a device copy of exactly the ragged
+batch's live K / V bytes and ``copy`` of all of them. With ``--fp8`` the same five over the FP8
+cache (``*_fp8``). ``ragged_over_uniform`` is the time ratio, ``live_share`` the byte ratio it
+would equal if time followed the live bytes alone.
 """
 
 from __future__ import annotations
@@ -150,6 +160,120 @@ def bench_row(B, H, D, L, args):
     return row
 
 
+def bench_ragged_row(B, H, D, L, args):
+    import torch
+
+    from distributed_llm_backend_benchmark_amd.ops import decode as dec
+
+    dev = torch.device("cuda", 0)
+    keys = [max(1, L * (b + 1) // B) for b in range(B)]          # keys row b attends, <= L
+    live_keys = sum(keys)
+    kv_bytes = 2 * B * H * L * D * 2
+    nbuf = max(1, min(16, -(-args.rotate_mb * (1 << 20) // kv_bytes)))
+    g = torch.Generator(device=dev).manual_seed(L + H)
+    caches = [torch.randn(2, B, H, L, D, generator=g, device=dev).to(torch.bfloat16)
+              for _ in range(nbuf)]
+    qkv = torch.randn(B, 1, 3 * H * D, generator=g, device=dev).to(torch.bfloat16)
+    shared = torch.tensor([L - 1], dtype=torch.int32, device=dev)
+    full = torch.full((B,), L - 1, dtype=torch.int32, device=dev)
+    ragged = torch.tensor([k - 1 for k in keys], dtype=torch.int32, device=dev)
+    ws = torch.empty(dec.workspace_numel(B, H, D, L, dec.CHUNK), dtype=torch.float32, device=dev)
+    # the live bytes as one flat run of a cache (K and V rows of H heads over sum(keys) positions)
+    live = 2 * H * live_keys * D
+    sink = torch.empty_like(caches[0])
+
+    def step(length):
+        def fn(i):
+            kc, vc = caches[i % nbuf]
+            return dec.decode_attention(qkv, H, kc, vc, length, workspace=ws)
+        return fn
+
+    def copy(n):
+        def fn(i):
+            sink.view(-1)[:n].copy_(caches[i % nbuf].view(-1)[:n])
+        return fn
+
+    cands = {"ragged": step(ragged), "uniform": step(shared), "uniform_seq": step(full),
+             "copy_live": copy(live), "copy": copy(sink.numel())}
+    nbytes = {"ragged": live * 2, "uniform": kv_bytes, "uniform_seq": kv_bytes,
+              "copy_live": live * 2, "copy": kv_bytes}
+    if args.fp8:
+        from distributed_llm_backend_benchmark_amd.ops import fp8
+
+        caches8 = []
+        for kv in caches:
+            q8, s8 = fp8.quantize_rows(kv.reshape(-1, D))
+            caches8.append((q8.view(2, B, H, L, D), s8.view(2, B, H, L)))
+        sink8 = (torch.empty_like(caches8[0][0]), torch.empty_like(caches8[0][1]))
+        ws8 = torch.empty(dec.workspace_numel(B, H, D, L, dec.CHUNK_FP8), dtype=torch.float32,
+                          device=dev)
+        rows_live = 2 * H * live_keys
+
+        def step8(length):
+            def fn(i):
+                (kc, vc), (ks, vs) = caches8[i % nbuf]
+                return dec.decode_attention(qkv, H, kc, vc, length, workspace=ws8, k_scale=ks,
+                                            v_scale=vs)
+            return fn
+
+        def copy8(rows):
+            def fn(i):
+                sink8[0].view(-1)[:rows * D].copy_(caches8[i % nbuf][0].view(-1)[:rows * D])
+                sink8[1].view(-1)[:rows].copy_(caches8[i % nbuf][1].view(-1)[:rows])
+            return fn
+
+        all_rows = 2 * B * H * L
+        cands.update({"ragged_fp8": step8(ragged), "uniform_fp8": step8(shared),
+                      "uniform_seq_fp8": step8(full), "copy_live_fp8": copy8(rows_live),
+                      "copy_fp8": copy8(all_rows)})
+        nbytes.update({"ragged_fp8": rows_live * (D + 4), "uniform_fp8": all_rows * (D + 4),
+                       "uniform_seq_fp8": all_rows * (D + 4),
+                       "copy_live_fp8": rows_live * (D + 4), "copy_fp8": all_rows * (D + 4)})
+
+    graphs = {}
+    for name, fn in cands.items():                       # warm every candidate, then capture
+        for i in range(nbuf + 1):
+            fn(i)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(args.inner):
+                fn(i)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    times = {n: [] for n in graphs}
+    for _ in range(args.rounds):                         # alternate the candidates
+        for name, gr in graphs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            gr.replay()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.inner)
+    # the per-sequence kernel at uniform lengths gives the shared-length kernel's bits
+    same = bool(torch.equal(step(full)(0).view(torch.int16), step(shared)(0).view(torch.int16)))
+    us = {n: statistics.median(v) for n, v in times.items()}
+    row = {"B": B, "H": H, "D": D, "L": L, "keys_per_row": keys, "kv_bytes": kv_bytes,
+           "live_kv_bytes": live * 2, "live_share": live_keys / (B * L), "rotated_caches": nbuf,
+           "chunk": dec.CHUNK, "inner": args.inner, "rounds": args.rounds, "us": us,
+           "us_min": {n: min(v) for n, v in times.items()},
+           "us_max": {n: max(v) for n, v in times.items()},
+           # bytes each candidate reads (a copy also writes them: its rate is over 2x)
+           "GBps": {n: (2 if n.startswith("copy") else 1) * nbytes[n] / (t * 1e-6) / 1e9
+                    for n, t in us.items()},
+           "uniform_seq_bits_equal_uniform": same,
+           "ragged_over_uniform": us["ragged"] / us["uniform"],
+           "uniform_seq_over_uniform": us["uniform_seq"] / us["uniform"],
+           "copy_live_over_copy": us["copy_live"] / us["copy"]}
+    if args.fp8:
+        row["live_kv_bytes_fp8"] = nbytes["ragged_fp8"]
+        row["chunk_fp8"] = dec.CHUNK_FP8
+        row["ragged_over_uniform_fp8"] = us["ragged_fp8"] / us["uniform_fp8"]
+        row["uniform_seq_over_uniform_fp8"] = us["uniform_seq_fp8"] / us["uniform_fp8"]
+    return row
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -158,17 +282,36 @@ def main(argv=None) -> int:
     ap.add_argument("--fp8", action="store_true",
                     help="also time the FP8 (e4m3) KV cache: ours_fp8, copy_fp8, --fp8-chunks")
     ap.add_argument("--fp8-chunks", type=int, nargs="*", default=[256, 512, 1024])
+    ap.add_argument("--ragged", action="store_true",
+                    help="time the per-sequence kernels on a batch of spread lengths instead: "
+                         "ragged, uniform, uniform_seq, copy_live, copy (with --fp8 also *_fp8)")
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--rotate-mb", type=int, default=512)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "decode",
-                                                  "attn_decode.jsonl"))
+    ap.add_argument("--out", default=None,
+                    help="default profiles/decode/attn_decode.jsonl (--ragged: "
+                         "profiles/ragged_decode/attn_decode_ragged.jsonl)")
     args = ap.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", *(("ragged_decode", "attn_decode_ragged.jsonl")
+                                                    if args.ragged
+                                                    else ("decode", "attn_decode.jsonl")))
     rows = ([tuple(int(v) for v in r.split(",")) for r in args.rows] if args.rows
             else DEFAULT_ROWS)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         for B, H, D, L in rows:
+            if args.ragged:
+                row = bench_ragged_row(B, H, D, L, args)
+                f.write(json.dumps(row) + "\n")
+                f.flush()
+                print(f"B={B} H={H} D={D} L={L} (live share {row['live_share']:.3f}): " +
+                      "  ".join(f"{n} {t:.1f} us ({row['GBps'][n]:.0f} GB/s)"
+                                for n, t in row["us"].items()) +
+                      f"  ragged/uniform {row['ragged_over_uniform']:.3f}" +
+                      (f"  fp8 {row['ragged_over_uniform_fp8']:.3f}" if args.fp8 else ""),
+                      flush=True)
+                continue
             row = bench_row(B, H, D, L, args)
             f.write(json.dumps(row) + "\n")
             f.flush()
