@@ -33,6 +33,15 @@ sequence_length]``; needs decode tokens and a real attention, composes with ``--
 ``--decode-weights``. The split grid is bounded by ``max + N``, the ``decode`` section carries
 ``prompt_lengths`` and counts the K / V bytes of the per-row lengths, the suffix ``_ragged`` comes
 last. The captured step replays as before: the lengths are device memory.
+``--kv-page-size P`` (``execution.kv_page_size``; 16 | 32 | 64 | 128 | 256) keeps the K / V of those
+steps in a PAGED cache (``ops.decode``): one pool of ``--kv-pages N`` (``execution.kv_pool_pages``;
+default ``sum_b ceil((len_b + N) / P)``, exactly what the run needs) pages per layer, shared by the
+rows through a block table. Needs decode tokens and a real attention; composes with
+``--prompt-lens`` (absent: every row at ``sequence_length``), ``--kv-cache fp8`` and
+``--decode-weights``. Every row's final length is reserved before the first forward, so the table
+never changes and the prefill and the step replay from their graphs. The ``decode`` section carries
+``kv_page_size``, ``kv_pool_pages`` and ``kv_pages_peak``, ``kv_cache_bytes_per_rank`` is the pools,
+and the suffix ``_paged<P>`` comes after ``_ragged``.
 """
 
 from __future__ import annotations
@@ -120,6 +129,16 @@ def parse_args(argv=None):
                          "(execution.prompt_lengths), one per batch row in [1, sequence_length], "
                          "decoded over a per-sequence KV cache; not with attention slice; output "
                          "file gets the suffix _ragged")
+    ap.add_argument("--kv-page-size", type=int, default=None, metavar="P",
+                    help="with --decode: a PAGED KV cache of pages of P positions "
+                         "(execution.kv_page_size; 16|32|64|128|256), shared by the batch rows "
+                         "through a block table; not with attention slice; composes with "
+                         "--prompt-lens, --kv-cache fp8 and --decode-weights; output file gets the "
+                         "suffix _paged<P>")
+    ap.add_argument("--kv-pages", type=int, default=None, metavar="N",
+                    help="with --kv-page-size: pages of the pool per layer "
+                         "(execution.kv_pool_pages; default: exactly what the run needs, "
+                         "sum_b ceil((len_b + N) / P))")
     ap.add_argument("--max-len", type=int, default=None, metavar="L",
                     help="with --decode: positions of the KV cache (default sequence_length + N)")
     ap.add_argument("--check-dense", action="store_true",
@@ -228,6 +247,41 @@ def main(argv=None) -> int:
     if n_dec and max_len < prompt + n_dec:
         print(f"ERROR: --max-len {max_len} < sequence_length {prompt} + {n_dec} decoded tokens")
         return 1
+    if args.kv_page_size is not None:
+        ex["kv_page_size"] = args.kv_page_size
+    if args.kv_pages is not None:
+        ex["kv_pool_pages"] = args.kv_pages
+    page, pool, row_tokens = ex.get("kv_page_size"), ex.get("kv_pool_pages"), None
+    if page is not None or pool is not None:
+        # refused before any process group exists, like --prompt-lens
+        from ..utils.config import KV_PAGE_SIZES
+
+        why = None
+        if page is None:
+            why = "--kv-pages (execution.kv_pool_pages) needs --kv-page-size P"
+        elif not n_dec:
+            why = ("--kv-page-size (execution.kv_page_size) needs decode tokens (--decode N): "
+                   "only the decode steps keep a KV cache")
+        elif ex.get("attention", "slice") == "slice":
+            why = ("--kv-page-size (execution.kv_page_size) needs attention sdpa or flash: "
+                   "attention slice keeps no K / V")
+        elif page not in KV_PAGE_SIZES:
+            why = (f"--kv-page-size (execution.kv_page_size) must be one of {KV_PAGE_SIZES}, "
+                   f"got {page}")
+        else:
+            # positions every row ends at: what the pool has to hold
+            row_tokens = [v + n_dec
+                          for v in (lens or [prompt] * int(config["input"]["batch_size"]))]
+            need = sum((v + page - 1) // page for v in row_tokens)
+            if pool is None:
+                pool = ex["kv_pool_pages"] = need
+            elif pool < need:
+                why = (f"--kv-pages (execution.kv_pool_pages) {pool} is too small: the rows "
+                       f"need {need} pages of {page} positions")
+        if why:
+            if os.environ.get("RANK", "0") == "0":
+                print(f"ERROR: {why}")
+            return 1
 
     t0 = time.perf_counter()
     cpr = config["parallelism"].get("cores_per_rank")
@@ -331,10 +385,22 @@ def main(argv=None) -> int:
     # --decode: the forward fills a KV cache (emptied before every call) and N one-token steps
     # follow it; without it `forward` is the model itself, as before
     cache = (model.new_kv_cache(int(config["input"]["batch_size"]), max_len,
-                                per_sequence=lens is not None) if n_dec else None)
+                                per_sequence=lens is not None, page_size=page, n_pages=pool)
+             if n_dec else None)
     if cache is not None:
         # split grid of the decode kernel: final position (of the longest row)
         cache.len_bound = (max(lens) if lens else prompt) + n_dec
+        if cache.paged:
+            # every page the run will touch, mapped once: the table then never changes, so the
+            # prefill and the decode step can be captured
+            cache.reserve_all(row_tokens)
+
+    def empty_cache():
+        """Every row back to length 0; a paged cache keeps its pages (set_length(0) frees them)."""
+        if cache.paged:
+            cache.set_length(0, keep_pages=True)
+        else:
+            cache.set_length(0)
 
     def forward(x):
         if cache is None:
@@ -346,7 +412,7 @@ def main(argv=None) -> int:
         batch = dataset.get_batch()
         b0 = model.comm_bytes()
         if cache is not None:
-            cache.set_length(0)
+            empty_cache()
         t = time.perf_counter()
         forward(batch)
         comm.sync()
@@ -385,14 +451,14 @@ def main(argv=None) -> int:
         try:
             side = torch.cuda.Stream(comm.device)
             if cache is not None:
-                cache.set_length(0)
+                empty_cache()
             side.wait_stream(torch.cuda.current_stream(comm.device))
             with torch.cuda.stream(side):
                 forward(static_in)
             torch.cuda.current_stream(comm.device).wait_stream(side)
             comm.sync()
             if cache is not None:
-                cache.set_length(0)
+                empty_cache()
                 comm.sync()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -436,7 +502,7 @@ def main(argv=None) -> int:
     for _ in range(int(ex["benchmark_iterations"])):
         comm.barrier()                          # reference run_mpi.py:177
         if cache is not None:
-            cache.set_length(0)
+            empty_cache()
         if gpu:
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
@@ -531,7 +597,8 @@ def main(argv=None) -> int:
             suffix += f"_{extra['gemm_dtype']}"
         if dec is not None:                    # never overwrites the prefill record
             suffix += f"_decode{n_dec}" + ("_w8" if w8 else "_w4" if w4 else "") + \
-                ("_kv8" if kv8 else "") + ("_ragged" if lens else "")
+                ("_kv8" if kv8 else "") + ("_ragged" if lens else "") + \
+                (f"_paged{page}" if page else "")
             d = results["decode"]
             print(f"  decode: {d['ms_per_token_mean']:.4f} ms/token ({d['timing_mode']}, "
                   f"attention {d['attention_path']}), {d['decode_tokens_per_s']:.0f} tokens/s, "
@@ -595,8 +662,12 @@ class _DecodeRunner:
         self.dev_ms, self.host_ms = [], []
         self.graph, self.graph_note = None, None
 
-        # warm: a prefill, then two eager steps at the first decode position
-        cache.set_length(0)
+        # warm: a prefill, then two eager steps at the first decode position (a paged cache was
+        # given all its pages by the caller: it is emptied without freeing them)
+        if cache.paged:
+            cache.set_length(0, keep_pages=True)
+        else:
+            cache.set_length(0)
         y = model(batch, kv_cache=cache, prompt_lens=lens)
         self.x.copy_(self._last_rows(y))
         b0, l0 = model.comm_bytes(), fp8.W8_LAUNCHES["count"]
@@ -725,6 +796,11 @@ class _DecodeRunner:
         }
         if self.lens:
             rec["prompt_lengths"] = list(self.lens)
+        if self.cache.paged:
+            # kv_cache_bytes_per_rank above is then the pools
+            rec["kv_page_size"] = self.cache.page_size
+            rec["kv_pool_pages"] = self.cache.n_pages
+            rec["kv_pages_peak"] = self.cache.peak_pages_in_use
         if w8:
             # the e4m3 bytes and row scales of every linear (+ the LayerNorm parameters): what a
             # step streams; weight_bytes_per_rank stays the resident bf16 footprint

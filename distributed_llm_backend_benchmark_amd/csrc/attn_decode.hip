@@ -13,6 +13,24 @@
 // (b, h, c, L) is that of the shared-length kernel, only where L comes from differs. The
 // shared-length forms (PerSeq = false) are instantiations of their own, compiled as before.
 //
+// Paged caches (the *_paged entry points): K / V live in pools k_pool / v_pool [n_pages, H, P, D]
+// (FP8: and k_scale / v_scale [n_pages, H, P]) shared by every batch row; the P rows of one
+// (page, head) are one contiguous run. `block_table` is int32[B, max_pages], max_pages =
+// ceil(L_max / P), one table for every layer: logical position t of row b lives in physical page
+// block_table[b, t / P] at row t % P. P is a power of two in [16, 256] that divides `chunk`, so a
+// chunk covers whole pages. `length` is always the per-sequence int32[B], and every *_seq rule
+// holds; L_max is the logical cap. An entry outside [0, n_pages) is an UNMAPPED page and never
+// becomes an address: a store to a position on it is dropped, a key on it below L is masked out
+// of the softmax and its loads are redirected to a row of the chunk's first mapped page (as
+// masked slots re-read a live row). The padded prefill relies on this rule. A chunk without any
+// mapped page writes the partial of no keys (m = -1e30, l = 0, o = 0); a live row with no mapped
+// key at all has no defined output. The kernels are the same templates with Paged = true: for a
+// given (b, h, chunk, L) a workgroup does the arithmetic of the *_seq kernel in the same order,
+// only the addresses differ, so with equal contents a row has the bits of the contiguous
+// per-sequence launch. A workgroup reads its chunk's <= 64 table entries once (one load per lane
+// of a wave, a ballot for the first mapped page) and keeps them in LDS; a key's page is one LDS
+// read. The combine kernel never sees the table.
+//
 //   bf16 cache  rows of D bf16 (2 D bytes).
 //   FP8 cache   rows of D e4m3fn bytes and k_scale / v_scale [B, H, L_max] fp32: one scale per
 //               cached row, row ~= float(code) * scale (D + 4 bytes a row). A row is quantised
@@ -100,10 +118,28 @@ struct KvAppendArgs {
   const int* length;
   int64_t ld;
   int B, T, H, D, L_max;
+  // Paged (after the contiguous forms' fields, whose offsets stay): k_cache / v_cache are the pools
+  const int* table;      // [B, tstride]
+  int64_t tstride;
+  int n_pages, psh;      // P = 1 << psh
 };
 
-// one 16-byte vector per thread step: (b, t, k|v, h, piece). PerSeq: length[b], not *length
-template <bool PerSeq>
+// row of a pool [n_pages, H, P, D] that holds logical position `pos` of head h in page pg
+__device__ __forceinline__ int64_t pool_row(int pg, int H, int h, int psh, int64_t pos) {
+  return ((static_cast<int64_t>(pg) * H + h) << psh) + (pos & ((1 << psh) - 1));
+}
+
+// the pool row of logical position `pos` of (b, h), -1 when its page is not mapped
+__device__ __forceinline__ int64_t paged_row(const int* table, int64_t tstride, int n_pages,
+                                             int psh, int H, int b, int h, int64_t pos) {
+  const int pg = table[b * tstride + (pos >> psh)];
+  if (pg < 0 || pg >= n_pages) return -1;
+  return pool_row(pg, H, h, psh, pos);
+}
+
+// one 16-byte vector per thread step: (b, t, k|v, h, piece). PerSeq: length[b], not *length.
+// Paged: the destination row comes through the block table, an unmapped one is dropped
+template <bool PerSeq, bool Paged>
 __global__ __launch_bounds__(256) void kv_append_kernel(KvAppendArgs a) {
   [[maybe_unused]] const int len0 = PerSeq ? 0 : *a.length;
   const int vpr = a.D / 8;                                  // vectors per head row
@@ -126,8 +162,15 @@ __global__ __launch_bounds__(256) void kv_append_kernel(KvAppendArgs a) {
     const u16x8 val = *reinterpret_cast<const u16x8*>(
         a.qkv + (static_cast<int64_t>(b) * a.T + t) * a.ld + static_cast<int64_t>(1 + kv) * a.H * a.D +
         hp * 8);
-    uint16_t* dst = (kv ? a.v_cache : a.k_cache) +
-                    ((static_cast<int64_t>(b) * a.H + h) * a.L_max + pos) * a.D + piece * 8;
+    uint16_t* dst;
+    if constexpr (Paged) {
+      const int64_t r = paged_row(a.table, a.tstride, a.n_pages, a.psh, a.H, b, h, pos);
+      if (r < 0) continue;
+      dst = (kv ? a.v_cache : a.k_cache) + r * a.D + piece * 8;
+    } else {
+      dst = (kv ? a.v_cache : a.k_cache) +
+            ((static_cast<int64_t>(b) * a.H + h) * a.L_max + pos) * a.D + piece * 8;
+    }
     *reinterpret_cast<u16x8*>(dst) = val;
   }
 }
@@ -141,11 +184,14 @@ struct KvAppend8Args {
   const int* length;
   int64_t ld;
   int B, T, H, L_max;
+  const int* table;      // Paged, as in KvAppendArgs
+  int64_t tstride;
+  int n_pages, psh;
 };
 
 // a row (b, t, k|v, h) of D bf16 per group of D / 8 lanes; uniform trip count over the grid, so
 // every lane of a group is active in the shuffles
-template <int D, bool PerSeq>
+template <int D, bool PerSeq, bool Paged>
 __global__ __launch_bounds__(256) void kv_append_fp8_kernel(KvAppend8Args a) {
   constexpr int LG = D / 8;                                 // lanes per row
   [[maybe_unused]] const int len0 = PerSeq ? 0 : *a.length;
@@ -178,7 +224,13 @@ __global__ __launch_bounds__(256) void kv_append_fp8_kernel(KvAppend8Args a) {
     else len = len0;
     const int64_t pos = static_cast<int64_t>(len) + t;
     if (!live || len < 0 || pos >= a.L_max) continue;       // device-side guard: never past the cache
-    const int64_t dst = (static_cast<int64_t>(b) * a.H + h) * a.L_max + pos;
+    int64_t dst;
+    if constexpr (Paged) {
+      dst = paged_row(a.table, a.tstride, a.n_pages, a.psh, a.H, b, h, pos);
+      if (dst < 0) continue;                                // an unmapped page: dropped
+    } else {
+      dst = (static_cast<int64_t>(b) * a.H + h) * a.L_max + pos;
+    }
     const u32x2 code{f32x4_to_e4m3(f[0] * inv, f[1] * inv, f[2] * inv, f[3] * inv),
                      f32x4_to_e4m3(f[4] * inv, f[5] * inv, f[6] * inv, f[7] * inv)};
     *reinterpret_cast<u32x2*>((kv ? a.v_cache : a.k_cache) + dst * D + piece * 8) = code;
@@ -198,7 +250,25 @@ struct DecodeArgs {
   int64_t ld, ldo;
   int B, H, L_max, chunk, n_chunks, fused;
   float scale_log2;
+  // Paged (after the contiguous forms' fields, whose offsets stay): k_cache / v_cache / k_scale /
+  // v_scale are the pools [n_pages, H, P, D] / [n_pages, H, P]
+  const int* table;      // [B, tstride]
+  int64_t tstride;
+  int n_pages, psh;      // P = 1 << psh
 };
+
+constexpr int kDecChunkPages = 64;     // table entries of one chunk: one per lane of a wave
+
+// the split kernel's LDS copy of its chunk's table entries (-1 = unmapped); no LDS when !Paged
+template <bool Paged>
+__device__ __forceinline__ int* chunk_pages() {
+  if constexpr (Paged) {
+    __shared__ int pages[kDecChunkPages];
+    return pages;
+  } else {
+    return nullptr;
+  }
+}
 
 // keys the step attends (and whether the new token has a cache slot): uniform, from device
 // memory. PerSeq: row b's own length; a negative one is an empty slot, 0 keys, len stays < 0
@@ -261,7 +331,7 @@ __device__ __forceinline__ void quant_row16(const uint16_t* p, u32x4& code, floa
                             f[4 * i + 3] * inv);
 }
 
-template <int D, typename Fmt, bool PerSeq>
+template <int D, typename Fmt, bool PerSeq, bool Paged>
 __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeArgs a) {
   using Elem = typename Fmt::Elem;
   using Frag = typename Fmt::Frag;
@@ -282,6 +352,38 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
   const int tid = threadIdx.x, sub = tid % LPK, slot = tid / LPK;
   // position whose K / V come from qkv (and are stored to the cache here); -1: none
   const int newpos = (a.fused && room) ? len : -1;
+
+  // Paged: the chunk's table entries, once per workgroup. Every wave loads them (one entry per
+  // lane: a chunk starts on a page edge and holds <= 64 pages), entries outside the pool become
+  // -1, the ballot gives the first mapped page: masked and unmapped keys re-read its row 0,
+  // logical position ksafe < k1 (a cached row, or the token: `fresh` below). Wave 0 keeps the
+  // entries in LDS for the per-key look-ups.
+  [[maybe_unused]] int* pages = chunk_pages<Paged>();
+  [[maybe_unused]] int ksafe = 0, pgsafe = 0;
+  if constexpr (Paged) {
+    const int ln = tid & (kWave - 1);
+    const int n_ent = (k1 - k0 + (1 << a.psh) - 1) >> a.psh;
+    int e = -1;
+    if (ln < n_ent) e = a.table[b * a.tstride + (k0 >> a.psh) + ln];
+    if (e < 0 || e >= a.n_pages) e = -1;
+    const unsigned long long mapped = __ballot(e >= 0);
+    if (mapped == 0) {                       // no mapped page: the partial of no keys
+      if (tid < D) {
+        float* p = a.ws + ((static_cast<int64_t>(b) * a.H + h) * a.n_chunks + c) * (D + 2);
+        p[2 + tid] = 0.f;
+        if (tid == 0) {
+          p[0] = kDecNegBig;
+          p[1] = 0.f;
+        }
+      }
+      return;
+    }
+    const int first = __builtin_ctzll(mapped);
+    ksafe = k0 + (first << a.psh);
+    pgsafe = __shfl(e, first, 64);
+    if (tid < kWave) pages[tid] = e;
+    __syncthreads();
+  }
 
   // The compiler's schedule and register allocation of the whole kernel follow the statement
   // order of this prologue and the way its address sums associate. Where the two formats differ
@@ -309,7 +411,10 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
   const int64_t rows = (static_cast<int64_t>(b) * a.H + h) * a.L_max;
   // the lane's columns of row 0 of (b, h): cache + rows * D + sub * C
   Elem *kc = reinterpret_cast<Elem*>(a.k_cache), *vc = reinterpret_cast<Elem*>(a.v_cache);
-  if constexpr (Fmt::kScaled) {
+  if constexpr (Paged) {                     // pool row 0; `rows` is not used
+    kc += sub * C;
+    vc += sub * C;
+  } else if constexpr (Fmt::kScaled) {
     kc = kc + rows * D + sub * C;
     vc = vc + rows * D + sub * C;
   } else {
@@ -323,12 +428,28 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
   [[maybe_unused]] Frag nk{}, nv{};
   [[maybe_unused]] float nks = 1.f, nvs = 1.f;
   if constexpr (Fmt::kScaled) {
-    ksc = a.k_scale + rows;
-    vsc = a.v_scale + rows;
+    if constexpr (Paged) {
+      ksc = a.k_scale;
+      vsc = a.v_scale;
+    } else {
+      ksc = a.k_scale + rows;
+      vsc = a.v_scale + rows;
+    }
     if (newpos >= k0 && newpos < k1) {
       quant_row16<LPK>(row + a.H * D, nk, nks);
       quant_row16<LPK>(row + 2 * a.H * D, nv, nvs);
-      if (slot == 0) {
+      if constexpr (Paged) {                 // through the table; dropped on an unmapped page
+        const int pg = pages[(newpos - k0) >> a.psh];
+        const int64_t nr = pool_row(pg, a.H, h, a.psh, newpos);
+        if (slot == 0 && pg >= 0) {
+          *reinterpret_cast<Frag*>(kc + nr * D) = nk;
+          *reinterpret_cast<Frag*>(vc + nr * D) = nv;
+          if (sub == 0) {
+            ksc[nr] = nks;
+            vsc[nr] = nvs;
+          }
+        }
+      } else if (slot == 0) {
         *reinterpret_cast<Frag*>(kc + static_cast<int64_t>(newpos) * D) = nk;
         *reinterpret_cast<Frag*>(vc + static_cast<int64_t>(newpos) * D) = nv;
         if (sub == 0) {
@@ -351,16 +472,24 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
     for (int u = 0; u < U; ++u) {
       const int key = it + u * NS + slot;
       ok[u] = key < k1;
-      const int kk = ok[u] ? key : k1 - 1;         // masked slots re-read a live row
+      int kk = ok[u] ? key : k1 - 1;               // masked slots re-read a live row
+      [[maybe_unused]] int64_t r = 0;              // Paged: the pool row holding key kk
+      if constexpr (Paged) {
+        const int pg = pages[(kk - k0) >> a.psh];
+        const bool mapped = pg >= 0;               // a key on an unmapped page is masked too
+        ok[u] = ok[u] && mapped;
+        kk = mapped ? kk : ksafe;
+        r = pool_row(mapped ? pg : pgsafe, a.H, h, a.psh, kk);
+      }
       const bool fresh = kk == newpos;
-      Elem* kp = kc + static_cast<int64_t>(kk) * D;
-      Elem* vp = vc + static_cast<int64_t>(kk) * D;
+      Elem* kp = kc + (Paged ? r : static_cast<int64_t>(kk)) * D;
+      Elem* vp = vc + (Paged ? r : static_cast<int64_t>(kk)) * D;
       if constexpr (Fmt::kScaled) {
         // row `newpos` is taken from the registers, never from what the loads below return for it
         // (slot 0's stores may or may not have landed): the loads stay in bounds, kk < L <= L_max
         const Frag kl = *reinterpret_cast<const Frag*>(kp);
         const Frag vl = *reinterpret_cast<const Frag*>(vp);
-        const float ksl = ksc[kk], vsl = vsc[kk];
+        const float ksl = Paged ? ksc[r] : ksc[kk], vsl = Paged ? vsc[r] : vsc[kk];
         kr[u] = fresh ? nk : kl;
         vr[u] = fresh ? nv : vl;
         ks[u] = fresh ? nks : ksl;
@@ -503,12 +632,30 @@ bool scales_ok(const void* k_scale, const void* v_scale) {
   return k_scale && v_scale && !mis(k_scale, 4) && !mis(v_scale, 4);
 }
 
-// validation and the split + combine launches of both decode entry points
-template <typename Fmt, bool PerSeq>
+// the block table of a paged launch (all zero for the contiguous forms)
+struct PageTable {
+  const void* table;     // int32[B, stride]
+  int64_t stride;
+  int n_pages, P;
+};
+
+// what the paged entry points ask of the table and the page size: P a power of two in [16, 256],
+// a row of the table covers L_max, and (decode: chunk > 0) a chunk is 1 .. 64 whole pages
+bool paged_ok(const PageTable& t, int L_max, int chunk, int& psh) {
+  if (!t.table || mis(t.table, 4) || t.n_pages <= 0) return false;
+  if (t.P < 16 || t.P > 256 || (t.P & (t.P - 1))) return false;
+  if (t.stride < (static_cast<int64_t>(L_max) + t.P - 1) / t.P) return false;
+  if (chunk > 0 && (chunk % t.P || chunk / t.P > kDecChunkPages)) return false;
+  psh = __builtin_ctz(t.P);
+  return true;
+}
+
+// validation and the split + combine launches of the decode entry points
+template <typename Fmt, bool PerSeq, bool Paged = false>
 int decode_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, void* k_scale,
                   void* v_scale, const void* length, void* ws, void* out, int64_t ldo, int B,
                   int H, int D, int L_max, int len_bound, int chunk, int fused, float scale,
-                  hipStream_t stream) {
+                  hipStream_t stream, const PageTable& pt = {}) {
   if (B <= 0 || H <= 0) return hipSuccess;
   if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
   if (PerSeq && !seq_length_ok(length)) return hipErrorInvalidValue;
@@ -516,61 +663,69 @@ int decode_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, voi
   if (!k_cache || !v_cache || !out) return hipErrorInvalidValue;
   if (Fmt::kScaled && !scales_ok(k_scale, v_scale)) return hipErrorInvalidValue;
   if (H > 65535 || B > 65535) return hipErrorInvalidValue;
+  int psh = 0;
+  if (Paged && !paged_ok(pt, L_max, chunk, psh)) return hipErrorInvalidValue;
   if (len_bound > L_max) len_bound = L_max;
   const int n_chunks = (len_bound + chunk - 1) / chunk;
   DecodeArgs a{static_cast<const uint16_t*>(qkv), static_cast<uint8_t*>(k_cache),
                static_cast<uint8_t*>(v_cache), static_cast<float*>(k_scale),
                static_cast<float*>(v_scale), static_cast<const int*>(length),
                static_cast<float*>(ws), static_cast<uint16_t*>(out), ld, ldo, B, H, L_max, chunk,
-               n_chunks, fused ? 1 : 0, scale * 1.4426950408889634f};
+               n_chunks, fused ? 1 : 0, scale * 1.4426950408889634f,
+               static_cast<const int*>(pt.table), pt.stride, pt.n_pages, psh};
   const dim3 gs(n_chunks, H, B), gc(H, B);
   if (D == 64) {
-    hipLaunchKernelGGL((attn_decode_split_kernel<64, Fmt, PerSeq>), gs, dim3(kDecThreads), 0,
-                       stream, a);
+    hipLaunchKernelGGL((attn_decode_split_kernel<64, Fmt, PerSeq, Paged>), gs, dim3(kDecThreads),
+                       0, stream, a);
     hipLaunchKernelGGL((attn_decode_combine_kernel<64, PerSeq>), gc, dim3(64), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((attn_decode_split_kernel<128, Fmt, PerSeq>), gs, dim3(kDecThreads), 0,
-                       stream, a);
+    hipLaunchKernelGGL((attn_decode_split_kernel<128, Fmt, PerSeq, Paged>), gs, dim3(kDecThreads),
+                       0, stream, a);
     hipLaunchKernelGGL((attn_decode_combine_kernel<128, PerSeq>), gc, dim3(128), 0, stream, a);
   }
   return hipGetLastError();
 }
 
-// validation and the launch of both bf16 append entry points
-template <bool PerSeq>
+// validation and the launch of the bf16 append entry points
+template <bool PerSeq, bool Paged = false>
 int append_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, const void* length,
-                  int B, int T, int H, int D, int L_max, hipStream_t stream) {
+                  int B, int T, int H, int D, int L_max, hipStream_t stream,
+                  const PageTable& pt = {}) {
   if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
   if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
   if (PerSeq && !seq_length_ok(length)) return hipErrorInvalidValue;
+  int psh = 0;
+  if (Paged && !paged_ok(pt, L_max, 0, psh)) return hipErrorInvalidValue;
   KvAppendArgs a{static_cast<const uint16_t*>(qkv), static_cast<uint16_t*>(k_cache),
                  static_cast<uint16_t*>(v_cache), static_cast<const int*>(length), ld, B, T, H, D,
-                 L_max};
+                 L_max, static_cast<const int*>(pt.table), pt.stride, pt.n_pages, psh};
   const int64_t vecs = static_cast<int64_t>(B) * T * 2 * H * (D / 8);
-  hipLaunchKernelGGL(kv_append_kernel<PerSeq>, dim3(stream_grid(vecs, 256)), dim3(256), 0, stream,
-                     a);
+  hipLaunchKernelGGL((kv_append_kernel<PerSeq, Paged>), dim3(stream_grid(vecs, 256)), dim3(256),
+                     0, stream, a);
   return hipGetLastError();
 }
 
-// the same for both FP8 append entry points
-template <bool PerSeq>
+// the same for the FP8 append entry points
+template <bool PerSeq, bool Paged = false>
 int append_fp8_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, void* k_scale,
                       void* v_scale, const void* length, int B, int T, int H, int D, int L_max,
-                      hipStream_t stream) {
+                      hipStream_t stream, const PageTable& pt = {}) {
   if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
   if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
   if (PerSeq && !seq_length_ok(length)) return hipErrorInvalidValue;
   if (!k_cache || !v_cache || !scales_ok(k_scale, v_scale)) return hipErrorInvalidValue;
+  int psh = 0;
+  if (Paged && !paged_ok(pt, L_max, 0, psh)) return hipErrorInvalidValue;
   KvAppend8Args a{static_cast<const uint16_t*>(qkv), static_cast<uint8_t*>(k_cache),
                   static_cast<uint8_t*>(v_cache), static_cast<float*>(k_scale),
                   static_cast<float*>(v_scale), static_cast<const int*>(length), ld, B, T, H,
-                  L_max};
+                  L_max, static_cast<const int*>(pt.table), pt.stride, pt.n_pages, psh};
   const int64_t lanes = static_cast<int64_t>(B) * T * 2 * H * (D / 8);
   const dim3 grid(stream_grid(lanes, 256));
   if (D == 64)
-    hipLaunchKernelGGL((kv_append_fp8_kernel<64, PerSeq>), grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((kv_append_fp8_kernel<64, PerSeq, Paged>), grid, dim3(256), 0, stream, a);
   else
-    hipLaunchKernelGGL((kv_append_fp8_kernel<128, PerSeq>), grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((kv_append_fp8_kernel<128, PerSeq, Paged>), grid, dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -660,4 +815,51 @@ DLBB_API int dlbb_attn_decode_fp8_seq(const void* qkv, int64_t ld, void* k_cache
                                       hipStream_t stream) {
   return decode_launch<KvE4m3, true>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, ws, out,
                                      ldo, B, H, D, L_max, len_bound, chunk, fused, scale, stream);
+}
+
+// The paged forms (file header): k_pool / v_pool [n_pages, H, P, D] (FP8: k_scale / v_scale
+// [n_pages, H, P]), block_table device int32[B, table_stride] with table_stride >= ceil(L_max / P),
+// length device int32[B] under the *_seq rules, L_max the logical cap. P must be a power of two in
+// [16, 256]; the decode forms also need chunk to be 1 .. 64 whole pages. Anything else, a null or
+// misaligned table or n_pages <= 0 returns hipErrorInvalidValue before any launch. A position
+// whose table entry lies outside [0, n_pages) is never stored to and never attended.
+DLBB_API int dlbb_kv_append_paged(const void* qkv, int64_t ld, void* k_pool, void* v_pool,
+                                  const void* length, const void* block_table,
+                                  int64_t table_stride, int n_pages, int P, int B, int T, int H,
+                                  int D, int L_max, hipStream_t stream) {
+  return append_launch<true, true>(qkv, ld, k_pool, v_pool, length, B, T, H, D, L_max, stream,
+                                   PageTable{block_table, table_stride, n_pages, P});
+}
+
+DLBB_API int dlbb_kv_append_fp8_paged(const void* qkv, int64_t ld, void* k_pool, void* v_pool,
+                                      void* k_scale, void* v_scale, const void* length,
+                                      const void* block_table, int64_t table_stride, int n_pages,
+                                      int P, int B, int T, int H, int D, int L_max,
+                                      hipStream_t stream) {
+  return append_fp8_launch<true, true>(qkv, ld, k_pool, v_pool, k_scale, v_scale, length, B, T, H,
+                                       D, L_max, stream,
+                                       PageTable{block_table, table_stride, n_pages, P});
+}
+
+DLBB_API int dlbb_attn_decode_paged(const void* qkv, int64_t ld, void* k_pool, void* v_pool,
+                                    const void* length, const void* block_table,
+                                    int64_t table_stride, int n_pages, int P, void* ws, void* out,
+                                    int64_t ldo, int B, int H, int D, int L_max, int len_bound,
+                                    int chunk, int fused, float scale, hipStream_t stream) {
+  return decode_launch<KvBf16, true, true>(qkv, ld, k_pool, v_pool, nullptr, nullptr, length, ws,
+                                           out, ldo, B, H, D, L_max, len_bound, chunk, fused,
+                                           scale, stream,
+                                           PageTable{block_table, table_stride, n_pages, P});
+}
+
+DLBB_API int dlbb_attn_decode_fp8_paged(const void* qkv, int64_t ld, void* k_pool, void* v_pool,
+                                        void* k_scale, void* v_scale, const void* length,
+                                        const void* block_table, int64_t table_stride,
+                                        int n_pages, int P, void* ws, void* out, int64_t ldo,
+                                        int B, int H, int D, int L_max, int len_bound, int chunk,
+                                        int fused, float scale, hipStream_t stream) {
+  return decode_launch<KvE4m3, true, true>(qkv, ld, k_pool, v_pool, k_scale, v_scale, length, ws,
+                                           out, ldo, B, H, D, L_max, len_bound, chunk, fused,
+                                           scale, stream,
+                                           PageTable{block_table, table_stride, n_pages, P});
 }

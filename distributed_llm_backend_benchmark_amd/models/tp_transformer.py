@@ -135,13 +135,33 @@ class TransformerBlock(nn.Module):
         ``ops.decode_attention``); ``sdpa`` and ``kernels="torch"`` the torch forms at the host
         position. The cache is advanced by the model, not here. A per-sequence cache hands its
         ``int32[B]`` ``length`` and its list of host positions through the same calls: the ops
-        dispatch on ``length.numel()``."""
+        dispatch on ``length.numel()``. A paged cache hands its pools, ``block_table`` and the
+        table's host mirror through as well."""
         from ..ops import decode as dec
 
         k, v = cache.k[layer], cache.v[layer]
         # the row scales of an FP8 cache (None for bf16): handed through as they are
         ks, vs = cache.k_scale[layer], cache.v_scale[layer]
         hip = self.attention == "flash" and self.kernels != "torch"
+        if cache.paged:
+            table = dict(block_table=cache.block_table, table_host=cache.table_host,
+                         max_len=cache.max_len)
+            if qkv.shape[1] == 1:
+                if hip:
+                    return ops.decode_attention(qkv, heads, k, v, cache.length,
+                                                len_bound=cache.len_bound,
+                                                workspace=cache.workspace, pos=cache.pos,
+                                                k_scale=ks, v_scale=vs, **table)
+                return dec.torch_decode_attention_paged(qkv, heads, k, v,
+                                                        cache.table_host.tolist(), cache.pos,
+                                                        ks, vs)
+            if hip:
+                ops.kv_append(qkv, heads, k, v, cache.length, pos=cache.pos, k_scale=ks,
+                              v_scale=vs, n_keep=cache.n_keep, **table)
+                return ops.causal_attention(qkv, heads)
+            dec.torch_kv_append_paged(qkv, heads, k, v, cache.table_host.tolist(), cache.pos,
+                                      ks, vs, cache.max_len)
+            return self._attn(qkv)
         if qkv.shape[1] == 1:
             if hip:
                 return ops.decode_attention(qkv, heads, k, v, cache.length,
@@ -236,7 +256,8 @@ class LLM(nn.Module):
                 return car
         return None
 
-    def new_kv_cache(self, batch: int, max_len: int, per_sequence: bool = False):
+    def new_kv_cache(self, batch: int, max_len: int, per_sequence: bool = False,
+                     page_size: Optional[int] = None, n_pages: Optional[int] = None):
         """A :class:`ops.KVCache` for this rank's ``num_heads / P`` local heads, ``max_len``
         positions. ``attention="slice"`` (the stateless stub) gets one with no K / V storage:
         decode still runs, and measures the GEMMs and the ``[B, 1, H]`` all-reduces alone.
@@ -244,7 +265,13 @@ class LLM(nn.Module):
         GEMM (``"mxfp4"``: of the W4 one): more than 16 rows raise here, not in the middle of a
         step. ``kv_cache_dtype`` picks the cache's storage (``"fp8"``: e4m3 codes + one fp32
         scale per row). ``per_sequence=True``: one length per batch row (``ops.decode``), for a
-        batch whose sequences differ in length; see :meth:`forward`."""
+        batch whose sequences differ in length; see :meth:`forward`. ``page_size`` (with
+        ``n_pages``, default: a page for every position of every row): a PAGED cache
+        (``ops.decode``): one pool of ``n_pages`` pages of ``page_size`` positions per layer,
+        shared by the rows through a block table; it is per-sequence."""
+        if page_size is not None and self.attention == "slice":
+            raise ValueError("a paged KV cache needs attention sdpa|flash: the slice stub keeps "
+                             "no K / V")
         if (self.decode_weight_dtype != "bf16" and batch > 16 and self.kernels != "torch"
                 and self.comm.device.type == "cuda" and not ops._lib.force_torch()):
             which = "W8" if self.decode_weight_dtype == "fp8" else "W4"
@@ -255,7 +282,7 @@ class LLM(nn.Module):
         layers = 0 if self.attention == "slice" else self.num_layers
         return ops.KVCache(layers, batch, heads, self.hidden_size // self.num_heads, max_len,
                            self.comm.device, kv_dtype=self.kv_cache_dtype,
-                           per_sequence=per_sequence)
+                           per_sequence=per_sequence, page_size=page_size, n_pages=n_pages)
 
     def _micro_batch(self, x: torch.Tensor, slot: int = 0, stream=None, cache=None):
         """One micro-batch's forward as a generator over its all-reduces (see
@@ -297,6 +324,14 @@ class LLM(nn.Module):
         any launch, and so does ``prompt_lens`` on a shared-length cache. One slot of such a
         cache is refilled through ``kv_cache.slot(b)``, a batch-1 shared-length cache.
 
+        With a paged cache (``new_kv_cache(..., page_size=P)``) the forward first reserves the
+        pages its tokens need (``prompt_lens[b]`` positions per live row for the padded prefill,
+        ``pos + T`` otherwise; a pool that cannot give them raises ``ValueError`` before any
+        launch). The padded prefill still appends all ``T`` rows: padding that falls on unmapped
+        pages is dropped on the device, padding inside the last mapped page lies past
+        ``length[b]`` and is overwritten as the row grows. ``kv_cache.slot(b)`` is then a batch-1
+        paged view.
+
         Without a cache — plain: one pass, each all-reduce inline. Overlapped (``overlap_chunks`` = n > 1): the
         batch is split into n micro-batches run round-robin, each advancing to its next
         all-reduce; the all-reduce goes to a side comm stream (normal priority: a high-priority one stretches
@@ -321,6 +356,11 @@ class LLM(nn.Module):
                 raise ValueError(f"prefill of {T} tokens on a cache holding {kv_cache.pos}: "
                                  "chunked prefill is not supported")
             kv_cache.check_room(T)
+            if kv_cache.paged:
+                keep = prompt_lens if prompt_lens is not None else [T] * x.shape[0]
+                kv_cache.reserve_all([min(max(p, 0) + n, kv_cache.max_len)
+                                      for p, n in zip(kv_cache.pos, keep)])
+                kv_cache.n_keep = prompt_lens
         n = 1 if kv_cache is not None else self.overlap_split(x)
         if n == 1:
             gen = self._micro_batch(x, cache=kv_cache)
@@ -329,6 +369,7 @@ class LLM(nn.Module):
                     next(gen)
             except StopIteration as e:
                 if kv_cache is not None:
+                    kv_cache.n_keep = None
                     if prompt_lens is not None:
                         # empty slots stay empty: their rows of the padded batch are not kept
                         kv_cache.set_lengths([n if p >= 0 else -1

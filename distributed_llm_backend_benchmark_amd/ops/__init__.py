@@ -29,10 +29,10 @@ from .optim import FlatAdamW
 from .clip import GradClipper, grad_sumsq, clip_coef, sumsq_plan
 from .xent import cross_entropy, linear_cross_entropy
 from .attention import causal_attention
-from .decode import KVCache, kv_append, decode_attention, CHUNK, CHUNK_FP8
+from .decode import KVCache, kv_append, decode_attention, CHUNK, CHUNK_FP8, PAGE_SIZE, PAGE_SIZES
 from .embedding import embedding
 
-__all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "CHUNK_FP8", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
+__all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "CHUNK_FP8", "PAGE_SIZE", "PAGE_SIZES", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
            "ChunkTable", "ScaleTable", "flatten_into", "linear", "layernorm", "bias_gelu",
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
            "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES",

@@ -180,6 +180,21 @@ _SIGS = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                          c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                          c_void_p]),
+    # paged pools (block_table, its row stride, n_pages, P after `length`)
+    "dlbb_kv_append_paged": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_void_p]),
+    "dlbb_kv_append_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                         c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dlbb_attn_decode_paged": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_int,
+                                       c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                       c_void_p]),
+    "dlbb_attn_decode_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                           c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                           c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "dlbb_rccl_unique_id_bytes": (c_int, []),
     "dlbb_rccl_get_unique_id": (c_int, [c_void_p]),
     "dlbb_rccl_init": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

@@ -42,6 +42,12 @@ Additions (all optional, defaults keep reference behaviour):
   of ``batch_size`` ints in ``[1, sequence_length]`` — the batch is right-padded prompts of these
   lengths and the decode steps run over a per-sequence KV cache (``ops.decode``;
   ``run_tp --prompt-lens``). Needs ``decode_tokens`` and a real attention.
+* ``execution.kv_page_size``: absent (default: contiguous caches) | one of 16, 32, 64, 128, 256 —
+  the decode steps run over a PAGED KV cache of pages of this many positions, shared by the batch
+  rows through a block table (``ops.decode``; ``run_tp --kv-page-size``). Needs ``decode_tokens``
+  and a real attention.
+* ``execution.kv_pool_pages``: absent (default: exactly the pages the run needs) | an int >= 1 —
+  the pages of that pool, per layer (``run_tp --kv-pages``). Needs ``kv_page_size``.
 """
 
 from __future__ import annotations
@@ -78,6 +84,9 @@ DEFAULT_CONFIG: Dict[str, Any] = {
     },
     "system": {"omp_num_threads": 14, "mkl_num_threads": 14},
 }
+
+# page sizes of the paged KV cache (ops.decode.PAGE_SIZES; not imported: no torch here)
+KV_PAGE_SIZES = (16, 32, 64, 128, 256)
 
 REQUIRED_SECTIONS = ("experiment", "model", "parallelism", "input", "execution", "system")
 
@@ -166,6 +175,15 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
                               f"{B}")
         if isinstance(S, int) and max(lens) > S:
             raise ConfigError(f"execution.prompt_lengths must lie in [1, sequence_length {S}]")
+    page, pool = ex.get("kv_page_size"), ex.get("kv_pool_pages")   # no defaults: absent = contiguous
+    if page is not None and (not isinstance(page, int) or isinstance(page, bool)
+                             or page not in KV_PAGE_SIZES):
+        raise ConfigError(f"execution.kv_page_size must be one of {KV_PAGE_SIZES}, got {page!r}")
+    if pool is not None:
+        if not isinstance(pool, int) or isinstance(pool, bool) or pool < 1:
+            raise ConfigError(f"execution.kv_pool_pages must be an int >= 1, got {pool!r}")
+        if page is None:
+            raise ConfigError("execution.kv_pool_pages needs execution.kv_page_size")
     return cfg
 
 

@@ -31,6 +31,16 @@ step over a batch whose rows attend ``L (b + 1) / B`` keys, b = 0 .. B - 1 (spre
 batch's live K / V bytes and ``copy`` of all of them. With ``--fp8`` the same five over the FP8
 cache (``*_fp8``). ``ragged_over_uniform`` is the time ratio, ``live_share`` the byte ratio it
 would equal if time followed the live bytes alone.
+
+``--paged`` times the paged kernels on the same ragged batches (same protocol, same process; rows
+go to ``profiles/paged_decode/attn_decode_paged.jsonl``). For every shape and each page size ``P``
+in ``--page-sizes`` (default 16, 64, 256): ``paged<P>`` is the decode step over a page pool holding
+exactly the live pages, the block table in a seeded shuffled physical order; ``paged_identity<P>``
+the same pool with every row's pages in logical order; beside them ``ragged`` (the contiguous
+per-sequence kernel at the same lengths) and ``copy_live``. With ``--fp8`` the same over the FP8
+cache (``*_fp8``). ``paged_over_ragged`` is the ratio of the medians per ``P``, ``ragged_spread``
+the min and max round of ``ragged`` over its median, and ``within_ragged_spread`` whether the
+ratio lies inside it; ``paged_bits_equal_ragged`` checks the outputs' bytes.
 """
 
 from __future__ import annotations
@@ -274,6 +284,146 @@ def bench_ragged_row(B, H, D, L, args):
     return row
 
 
+def bench_paged_row(B, H, D, L, args):
+    import torch
+
+    from distributed_llm_backend_benchmark_amd.ops import decode as dec
+
+    dev = torch.device("cuda", 0)
+    keys = [max(1, L * (b + 1) // B) for b in range(B)]          # keys row b attends, <= L
+    live_keys = sum(keys)
+    kv_bytes = 2 * B * H * L * D * 2
+    nbuf = max(1, min(16, -(-args.rotate_mb * (1 << 20) // kv_bytes)))
+    g = torch.Generator(device=dev).manual_seed(L + H)
+    caches = [torch.randn(2, B, H, L, D, generator=g, device=dev).to(torch.bfloat16)
+              for _ in range(nbuf)]
+    qkv = torch.randn(B, 1, 3 * H * D, generator=g, device=dev).to(torch.bfloat16)
+    ragged = torch.tensor([k - 1 for k in keys], dtype=torch.int32, device=dev)
+    ws = torch.empty(dec.workspace_numel(B, H, D, L, dec.CHUNK), dtype=torch.float32, device=dev)
+    live = 2 * H * live_keys * D
+    sink = torch.empty_like(caches[0])
+    caches8 = []
+    if args.fp8:
+        from distributed_llm_backend_benchmark_amd.ops import fp8
+
+        for kv in caches:
+            q8, s8 = fp8.quantize_rows(kv.reshape(-1, D))
+            caches8.append((q8.view(2, B, H, L, D), s8.view(2, B, H, L)))
+        sink8 = (torch.empty_like(caches8[0][0]), torch.empty_like(caches8[0][1]))
+        ws8 = torch.empty(dec.workspace_numel(B, H, D, L, dec.CHUNK_FP8), dtype=torch.float32,
+                          device=dev)
+
+    def tables(P, shuffled):
+        """The block table of the batch (exactly the live pages) and the pool size."""
+        need = [-(-k // P) for k in keys]
+        n_pages = sum(need)
+        order = (torch.randperm(n_pages, generator=torch.Generator().manual_seed(P + L)).tolist()
+                 if shuffled else list(range(n_pages)))
+        table = torch.full((B, -(-L // P)), -1, dtype=torch.int32)
+        for b in range(B):
+            for j in range(need[b]):
+                table[b, j] = order.pop(0)
+        return table, n_pages
+
+    def pooled(x, table, n_pages, P):
+        """``x [2, B, H, L, ...]`` -> the pool ``[2, n_pages, H, P, ...]`` through ``table``."""
+        pool = torch.zeros(2, n_pages, H, P, *x.shape[4:], dtype=x.dtype, device=dev)
+        raw, src = (t.view(torch.uint8) if t.dtype == dec.E4M3 else t for t in (pool, x))
+        for b in range(B):
+            idx = table[b][table[b] >= 0].to(dev).long()
+            n = idx.numel()
+            rows = src[:, b, :, :n * P].reshape(2, H, n, P, *x.shape[4:])
+            raw[:, idx] = rows.transpose(1, 2)
+        return pool
+
+    def step(length, bufs, wsp, **kw):
+        def fn(i):
+            (kc, vc), sc = bufs[i % nbuf]
+            return dec.decode_attention(qkv, H, kc, vc, length, workspace=wsp,
+                                        **({} if sc is None
+                                           else dict(k_scale=sc[0], v_scale=sc[1])), **kw)
+        return fn
+
+    def copy(n):
+        def fn(i):
+            sink.view(-1)[:n].copy_(caches[i % nbuf].view(-1)[:n])
+        return fn
+
+    cands = {"ragged": step(ragged, [(c, None) for c in caches], ws), "copy_live": copy(live)}
+    if args.fp8:
+        rows_live = 2 * H * live_keys
+
+        def copy8(i):
+            sink8[0].view(-1)[:rows_live * D].copy_(caches8[i % nbuf][0].view(-1)[:rows_live * D])
+            sink8[1].view(-1)[:rows_live].copy_(caches8[i % nbuf][1].view(-1)[:rows_live])
+
+        cands["ragged_fp8"] = step(ragged, caches8, ws8)
+        cands["copy_live_fp8"] = copy8
+    pool_pages = {}
+    for P in args.page_sizes:
+        if L % P or dec.CHUNK % P:
+            raise SystemExit(f"--paged needs page sizes dividing L = {L} and the chunk")
+        for name, shuffled in ((f"paged{P}", True), (f"paged_identity{P}", False)):
+            table, n_pages = tables(P, shuffled)
+            pool_pages[P] = n_pages
+            kw = dict(block_table=table.to(dev), max_len=L)
+            cands[name] = step(ragged, [(pooled(c, table, n_pages, P), None) for c in caches],
+                               ws, **kw)
+            if args.fp8:
+                cands[name + "_fp8"] = step(
+                    ragged, [(pooled(c8, table, n_pages, P), pooled(s8, table, n_pages, P))
+                             for c8, s8 in caches8], ws8, **kw)
+
+    graphs = {}
+    for name, fn in cands.items():                       # warm every candidate, then capture
+        for i in range(nbuf + 1):
+            fn(i)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(args.inner):
+                fn(i)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    times = {n: [] for n in graphs}
+    for _ in range(args.rounds):                         # alternate the candidates
+        for name, gr in graphs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            gr.replay()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.inner)
+    us = {n: statistics.median(v) for n, v in times.items()}
+    ref = cands["ragged"](0).view(torch.int16)
+    same = {n: bool(torch.equal(fn(0).view(torch.int16), ref)) for n, fn in cands.items()
+            if n.startswith("paged") and not n.endswith("_fp8")}
+    row = {"B": B, "H": H, "D": D, "L": L, "keys_per_row": keys, "kv_bytes": kv_bytes,
+           "live_kv_bytes": live * 2, "live_share": live_keys / (B * L), "rotated_caches": nbuf,
+           "chunk": dec.CHUNK, "inner": args.inner, "rounds": args.rounds,
+           "page_sizes": list(args.page_sizes), "pool_pages": pool_pages, "us": us,
+           "us_min": {n: min(v) for n, v in times.items()},
+           "us_max": {n: max(v) for n, v in times.items()},
+           "paged_bits_equal_ragged": same}
+    for sfx in ("", "_fp8") if args.fp8 else ("",):
+        lo, hi = (min(times["ragged" + sfx]) / us["ragged" + sfx],
+                  max(times["ragged" + sfx]) / us["ragged" + sfx])
+        row["ragged_spread" + sfx] = [lo, hi]
+        row["paged_over_ragged" + sfx] = {P: us[f"paged{P}{sfx}"] / us["ragged" + sfx]
+                                          for P in args.page_sizes}
+        row["paged_identity_over_ragged" + sfx] = {
+            P: us[f"paged_identity{P}{sfx}"] / us["ragged" + sfx] for P in args.page_sizes}
+        row["within_ragged_spread" + sfx] = {P: bool(r <= hi) for P, r in
+                                             row["paged_over_ragged" + sfx].items()}
+    if args.fp8:
+        ref8 = cands["ragged_fp8"](0).view(torch.int16)
+        row["paged_bits_equal_ragged_fp8"] = {
+            n: bool(torch.equal(fn(0).view(torch.int16), ref8)) for n, fn in cands.items()
+            if n.startswith("paged") and n.endswith("_fp8")}
+    return row
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -285,6 +435,10 @@ def main(argv=None) -> int:
     ap.add_argument("--ragged", action="store_true",
                     help="time the per-sequence kernels on a batch of spread lengths instead: "
                          "ragged, uniform, uniform_seq, copy_live, copy (with --fp8 also *_fp8)")
+    ap.add_argument("--paged", action="store_true",
+                    help="time the paged kernels on the ragged batches instead: paged<P>, "
+                         "paged_identity<P>, ragged, copy_live (with --fp8 also *_fp8)")
+    ap.add_argument("--page-sizes", type=int, nargs="*", default=[16, 64, 256])
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--rotate-mb", type=int, default=512)
@@ -293,7 +447,9 @@ def main(argv=None) -> int:
                          "profiles/ragged_decode/attn_decode_ragged.jsonl)")
     args = ap.parse_args(argv)
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", *(("ragged_decode", "attn_decode_ragged.jsonl")
+        args.out = os.path.join(REPO, "profiles", *(("paged_decode", "attn_decode_paged.jsonl")
+                                                    if args.paged else
+                                                    ("ragged_decode", "attn_decode_ragged.jsonl")
                                                     if args.ragged
                                                     else ("decode", "attn_decode.jsonl")))
     rows = ([tuple(int(v) for v in r.split(",")) for r in args.rows] if args.rows
@@ -301,6 +457,16 @@ def main(argv=None) -> int:
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         for B, H, D, L in rows:
+            if args.paged:
+                row = bench_paged_row(B, H, D, L, args)
+                f.write(json.dumps(row) + "\n")
+                f.flush()
+                print(f"B={B} H={H} D={D} L={L} (live share {row['live_share']:.3f}): " +
+                      "  ".join(f"{n} {t:.1f} us" for n, t in row["us"].items()) +
+                      f"  paged/ragged {row['paged_over_ragged']}  ragged spread "
+                      f"{row['ragged_spread']}" +
+                      (f"  fp8 {row['paged_over_ragged_fp8']}" if args.fp8 else ""), flush=True)
+                continue
             if args.ragged:
                 row = bench_ragged_row(B, H, D, L, args)
                 f.write(json.dumps(row) + "\n")
