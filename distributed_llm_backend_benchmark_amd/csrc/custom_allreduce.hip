@@ -654,6 +654,7 @@ struct CarState {
   Signal* sig = nullptr;      // uncached, IPC
   bool opened = false;
   bool local = false;         // virtual rank: peers are sibling states in this process (no IPC)
+  int sharers = 1;            // ranks (processes) launching on this GPU (dlbb_car_set_sharers)
   CarKernelArgs args{};
   char* peer_data[kMaxRanks] = {};
   char* peer_tmp[kMaxRanks] = {};
@@ -868,6 +869,31 @@ static int clamp_blocks(int nblocks) {
   return nblocks < 1 ? 1 : nblocks > kMaxBlocks ? kMaxBlocks : nblocks;
 }
 
+// Ranks that share one GPU (several processes on one device: rehearsals, tests): workgroup b of a
+// rank spins on workgroup b of every peer, so sharers x nblocks workgroups have to be resident at
+// once. A larger grid makes no progress until the driver time-slices the processes, which it may
+// not do within the wait bound. The grid is cut to the device's resident workgroups / sharers —
+// the same number on every rank (same kernel, same device). One rank per GPU: nothing changes.
+DLBB_API int dlbb_car_set_sharers(void* h, int n) {
+  CarState* s = static_cast<CarState*>(h);
+  if (!s || n < 1 || n > kMaxRanks) return hipErrorInvalidValue;
+  s->sharers = n;
+  return hipSuccess;
+}
+
+static int car_grid(const CarState* s, const void* fn, int nblocks, int* out) {
+  int nb = clamp_blocks(nblocks);
+  if (s->sharers > 1) {
+    int per_cu = 0, cus = 0;
+    CAR_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kCarThreads, 0));
+    CAR_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
+    const int fit = per_cu * cus / s->sharers;
+    if (nb > fit) nb = fit < 1 ? 1 : fit;
+  }
+  *out = nb;
+  return hipSuccess;
+}
+
 static int car_launch_rank(CarState* s, int kind, const void* inp, void* out, int64_t count,
                            int dtype, int id, int nblocks, hipStream_t stream) {
   CarKernelArgs a;
@@ -882,7 +908,9 @@ static int car_launch_rank(CarState* s, int kind, const void* inp, void* out, in
   const void* fn = car_kernel<false>(kind, dtype, s->world);
   if (!fn) return hipErrorInvalidValue;
   void* args[] = {&a};
-  CAR_CHECK(hipLaunchKernel(fn, dim3(clamp_blocks(nblocks)), dim3(kCarThreads), args, 0, stream));
+  int nb = 0;
+  CAR_CHECK(static_cast<hipError_t>(car_grid(s, fn, nblocks, &nb)));
+  CAR_CHECK(hipLaunchKernel(fn, dim3(nb), dim3(kCarThreads), args, 0, stream));
   return hipSuccess;
 }
 
@@ -1058,7 +1086,9 @@ DLBB_API int dlbb_car_alltoallv_reg(void* h, int id, const int64_t* src_off, con
   const void* fn = car_kernel<false>(K_A2AV, DT_BF16, s->world);
   if (!fn) return hipErrorInvalidValue;
   void* args[] = {&a};
-  CAR_CHECK(hipLaunchKernel(fn, dim3(clamp_blocks(nblocks)), dim3(kCarThreads), args, 0, stream));
+  int nb = 0;
+  CAR_CHECK(static_cast<hipError_t>(car_grid(s, fn, nblocks, &nb)));
+  CAR_CHECK(hipLaunchKernel(fn, dim3(nb), dim3(kCarThreads), args, 0, stream));
   return hipSuccess;
 }
 

@@ -213,6 +213,7 @@ _SIGS = {
     "dlbb_car_handle_bytes": (c_int, []),
     "dlbb_car_open": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_int)]),
     "dlbb_car_capacity": (c_int64, [c_void_p]),
+    "dlbb_car_set_sharers": (c_int, [c_void_p, c_int]),
     "dlbb_car_allreduce": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                    c_void_p]),
     "dlbb_car_reg_export": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64)]),

@@ -13,7 +13,8 @@ serves the direct one-hop ``all_gather_registered`` / ``reduce_scatter_registere
 
 Setup: each rank allocates its IPC regions, the 192-byte handles and device ordinals are
 exchanged once through the process group (``all_gather_object``), peers are opened with
-``hipIpcOpenMemHandle``. ``auto`` selection uses the custom kernel only below a crossover
+``hipIpcOpenMemHandle``. Ranks found on one GPU (same PCI address: rehearsals, tests) have their
+grids cut so that all of them stay resident together (``sharers``). ``auto`` selection uses the custom kernel only below a crossover
 size and only after a start-up self-test against RCCL passed on every rank.
 """
 
@@ -84,13 +85,23 @@ class CustomAllReduce:
             mine = bytes(buf.raw)
         except Exception as e:  # noqa: BLE001 - reported collectively below
             err = e
-        allh = comm.all_gather_object((mine, torch.cuda.current_device(), repr(err)))
+        from ..utils.affinity import device_bdf
+
+        allh = comm.all_gather_object((mine, torch.cuda.current_device(), repr(err),
+                                       device_bdf(torch.cuda.current_device())))
         if any(x[0] is None for x in allh):
             self.close()
             raise RuntimeError(f"custom all-reduce setup failed: {[x[2] for x in allh]}")
         blob = b"".join(x[0] for x in allh)
         devs = (ctypes.c_int * comm.world_size)(*[int(x[1]) for x in allh])
         rc = self.lib.dlbb_car_open(self.h, blob, devs)
+        # ranks sharing one GPU (same PCI address; rehearsals and tests) must all be resident at
+        # once: the library cuts every grid to its share of the device (csrc, car_grid). The
+        # largest group counts, so every rank launches the same grid.
+        bdfs = [x[3] for x in allh if x[3] is not None]
+        self.sharers = max([bdfs.count(b) for b in bdfs], default=1)
+        if rc == 0:
+            rc = self.lib.dlbb_car_set_sharers(self.h, self.sharers)
         oks = comm.all_gather_object(rc)
         if any(r != 0 for r in oks):
             self.close()

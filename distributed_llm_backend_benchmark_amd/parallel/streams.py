@@ -13,7 +13,7 @@ created before — measured on MI355X (``profiles/r03_tp/overlap_probe``, ``prof
   100 GB/s), a different one after changing the communicator init — the stall moved with the
   stream order, not with the configuration.
 
-:func:`concurrent_stream` therefore PROBES candidates: a 1-workgroup spin kernel (~100 us) on
+:func:`concurrent_stream` therefore PROBES candidates: a 1-workgroup spin kernel (400 us) on
 the reference (compute) stream and one on the candidate, started together; if the pair takes
 about one spin, the candidate runs concurrently. It also has to run beside every side stream
 handed out before on that device (DDP's weight-gradient and comm streams must not share a queue
@@ -32,7 +32,12 @@ _CACHE: Dict[Tuple[int, str, int], "torch.cuda.Stream"] = {}
 # — result JSONs carry it so a rocprofv3 kernel trace's Stream_Id / Queue_Id columns can be
 # matched to roles
 LOG: list = []
-_PROBE_NS = 100_000
+# The probe decides with a margin of half a spin, and a pair on two streams also pays a fixed cost
+# the one-stream baselines do not (event record, cross-stream wait, join). Measured on a
+# virtualised host it is 40-60 us for a concurrent pair and ~25 us for a serialised one, whatever the spin:
+# the whole margin of a 100 us spin, where concurrent pairs (145-180 us) straddled the 166 us
+# threshold. At 400 us the margin is 200 us, several times that cost on either side.
+_PROBE_NS = 400_000
 _TRIES = 12
 
 
