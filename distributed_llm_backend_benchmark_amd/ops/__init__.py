@@ -23,7 +23,8 @@ from .elementwise import reduce_sum, cast, pack_rows, ChunkTable, ScaleTable, fl
 from .gemm import linear
 from .fp8 import quantize_rows, linear_fp8, fp8_linear, linear_w8, w8_linear, W8_LAUNCHES
 from .mxfp4 import (quantize_mxfp4, dequantize_mxfp4, quantize_weight_mxfp4, linear_w4,
-                    w4_linear, w4_contract_error, w4_skinny_plan, W4_LAUNCHES)
+                    w4_linear, w4_contract_error, w4_skinny_plan, W4_LAUNCHES,
+                    quantize_rows_mxfp4, linear_mxfp4, mxfp4_linear)
 from .norm_act import layernorm, bias_gelu
 from .optim import FlatAdamW
 from .clip import GradClipper, grad_sumsq, clip_coef, sumsq_plan
@@ -37,5 +38,6 @@ __all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "CHUNK_FP8", "PA
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
            "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES",
            "quantize_mxfp4", "dequantize_mxfp4", "quantize_weight_mxfp4", "linear_w4",
-           "w4_linear", "w4_contract_error", "w4_skinny_plan", "W4_LAUNCHES", "GradClipper",
+           "w4_linear", "w4_contract_error", "w4_skinny_plan", "W4_LAUNCHES",
+           "quantize_rows_mxfp4", "linear_mxfp4", "mxfp4_linear", "GradClipper",
            "grad_sumsq", "clip_coef", "sumsq_plan"]

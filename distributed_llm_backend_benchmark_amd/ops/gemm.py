@@ -1011,4 +1011,6 @@ def kernel_mix() -> dict:
     out["layernorm_bwd_fallbacks"] = LN_FALLBACKS["count"]
     from . import fp8                                 # FP8 GEMM launches + distinct shapes
     out["fp8"] = fp8.kernel_mix()
+    from . import mxfp4                               # MXFP4 GEMM launches + distinct shapes
+    out["mxfp4"] = mxfp4.kernel_mix()
     return out

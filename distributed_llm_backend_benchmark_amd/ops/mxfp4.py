@@ -34,6 +34,14 @@ multiplies with the bf16 activation as it is. Opt-in (``decode_weight_dtype="mxf
 tensor the HIP kernel is the only implementation and a shape outside its contract raises. The
 weight is quantised once, in torch on its own device (there is no HIP quantiser), before any
 graph capture.
+
+``csrc/gemm_mxfp4.hip`` (:func:`quantize_rows_mxfp4` / :func:`linear_mxfp4` /
+:func:`mxfp4_linear`) is the large-M form, for linears of the size of the TP forward's: the
+activation is quantised per call by a HIP kernel that produces exactly the bits of
+:func:`_quantize_rows`, and both operands stay MXFP4 on the block-scaled MFMA
+(``v_mfma_scale_f32_16x16x128_f8f6f4`` with e2m1 operands and the e8m0 scales applied by the
+instruction). Called explicitly (the TP layers' ``gemm_dtype`` does not offer it yet), and no
+fall-back either.
 """
 
 from __future__ import annotations
@@ -55,6 +63,10 @@ SCALE_MIN, SCALE_MAX = 2, 252             # the range of emitted scale bytes (mo
 _CHUNK_ELEMS = 1 << 22                    # fp32 temporaries of the quantiser: 16 MiB each
 
 W4_LAUNCHES = {"count": 0}                # launches of the W4 skinny kernel itself
+QUANT_MAX_K = 16384                       # the row quantiser keeps a row in one workgroup
+CALLS = {}                # (M, N, K) -> MXFP4 GEMM launches since import (kernel_mix()["mxfp4"])
+_MX_CONTRACT = ("contract: K % 256 == 0, M % 8 == 0, N % 64 == 0; there is no fall-back to "
+                "bf16")
 
 _W4_CONTRACT = ("contract: 1 <= M <= 16, N % 16 == 0, K % 128 == 0; there is no fall-back to "
                 "bf16")
@@ -285,3 +297,155 @@ def w4_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = N
             raise ValueError(f"w4_linear: {why} ({_W4_CONTRACT})")
     codes, scales = quantize_weight_mxfp4(w)
     return linear_w4(x, codes, scales, bias, act, residual, out_dtype, out, kernels=kernels)
+
+
+# ---- MXFP4 x MXFP4 GEMM of the TP forward: csrc/gemm_mxfp4.hip ---------------------------------
+
+def quantize_rows_mxfp4(x: torch.Tensor,
+                        kernels: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``x [..., K]`` -> ``(codes uint8 [..., K/2], scales uint8 [..., K/32])`` (module docstring
+    for the exact semantics). HIP on a GPU bf16 tensor with ``K % 32 == 0``, ``K <= 16384`` and
+    16-byte aligned rows (rows may be strided); :func:`_quantize_rows` otherwise. Both produce the
+    same bits."""
+    K = x.shape[-1]
+    lead = x.shape[:-1]
+    if K % BLOCK or K == 0:
+        raise ValueError(f"quantize_rows_mxfp4: K = {K} is not a positive multiple of {BLOCK}")
+    x2 = x if x.dim() == 2 else x.reshape(-1, K)
+    M = x2.shape[0]
+    hip = (_want_hip(kernels, x) and x.dtype == torch.bfloat16 and K <= QUANT_MAX_K and M > 0
+           and x2.stride(1) == 1 and x2.data_ptr() % 16 == 0
+           and (M == 1 or (x2.stride(0) % 8 == 0 and x2.stride(0) >= K)))
+    if not hip:
+        codes, scales = _quantize_rows(x2.float())
+        return codes.reshape(*lead, K // 2), scales.reshape(*lead, K // BLOCK)
+    codes = torch.empty(M, K // 2, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(M, K // BLOCK, dtype=torch.uint8, device=x.device)
+    check(_lib.lib().dlbb_quant_mxfp4_rows(
+        x2.data_ptr(), x2.stride(0) if M > 1 else K, codes.data_ptr(), K // 2,
+        scales.data_ptr(), K // BLOCK, M, K, _lib.stream(x.device)), "quant_mxfp4_rows")
+    return codes.view(*lead, K // 2), scales.view(*lead, K // BLOCK)
+
+
+def gemm_contract_error(M: int, N: int, K: int) -> Optional[str]:
+    """Why (M, N, K) is outside the MXFP4 GEMM kernel's shape contract, or None."""
+    if M <= 0 or N <= 0 or K <= 0:
+        return "empty operand"
+    if K % 256:
+        return f"K = {K} is not a multiple of 256"
+    if M % 8:
+        return f"M = {M} is not a multiple of 8"
+    if N % 64:
+        return f"N = {N} is not a multiple of 64"
+    return None
+
+
+def linear_mxfp4(xc: torch.Tensor, xs: torch.Tensor, wc: torch.Tensor, ws: torch.Tensor,
+                 bias: Optional[torch.Tensor] = None, act: Optional[str] = None,
+                 residual: Optional[torch.Tensor] = None,
+                 out_dtype: torch.dtype = torch.bfloat16, out: Optional[torch.Tensor] = None,
+                 kernels: Optional[str] = None) -> torch.Tensor:
+    """``act(dequantize_mxfp4(xc, xs) @ dequantize_mxfp4(wc, ws).T + bias) + residual``.
+
+    ``xc [..., K/2]`` / ``wc [N, K/2]`` uint8 e2m1 pairs (unit column stride), ``xs [..., K/32]``
+    / ``ws [N, K/32]`` uint8 e8m0 scales, ``bias [N]`` / ``residual [..., N]`` bf16; fp32
+    accumulation, bf16 or fp32 result ``[..., N]``.
+
+    HIP contract: ``K % 256 == 0``, ``M % 8 == 0`` (M = rows of ``xc``), ``N % 64 == 0``, 16-byte
+    aligned code rows, 8-byte aligned scale rows. Anything else raises ``ValueError`` before any
+    launch."""
+    if act not in ACTS:
+        raise ValueError(f"unknown activation {act!r}")
+    if xc.dtype != torch.uint8 or wc.dtype != torch.uint8 or xs.dtype != torch.uint8 \
+            or ws.dtype != torch.uint8:
+        raise ValueError("linear_mxfp4: codes and scales must be uint8")
+    K = xc.shape[-1] * 2
+    N = wc.shape[0]
+    lead = xc.shape[:-1]
+    if wc.dim() != 2 or wc.shape[1] * 2 != K:
+        raise ValueError(f"linear_mxfp4: xc[..., {K // 2}] vs wc{tuple(wc.shape)}")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("linear_mxfp4: out_dtype must be bf16 or fp32")
+    x2 = xc.reshape(-1, K // 2)
+    M = x2.shape[0]
+    if K % BLOCK or xs.numel() != M * (K // BLOCK) or xs.shape[-1] != K // BLOCK \
+            or tuple(ws.shape) != (N, K // BLOCK):
+        raise ValueError(f"linear_mxfp4: scales must be [..., K / {BLOCK}]: xs{tuple(xs.shape)}, "
+                         f"ws{tuple(ws.shape)} for M = {M}, N = {N}, K = {K}")
+    xs2 = xs.reshape(M, K // BLOCK)
+    if not _want_hip(kernels, xc, wc):
+        y = dequantize_mxfp4(x2, xs2) @ dequantize_mxfp4(wc, ws).t()
+        y = _epilogue_torch(y, bias, act, None if residual is None else residual.reshape(M, N),
+                            out_dtype).reshape(*lead, N)
+        return y if out is None else out.copy_(y.reshape(out.shape))
+    why = gemm_contract_error(M, N, K)
+    if why:
+        raise ValueError(f"linear_mxfp4: {why} ({_MX_CONTRACT})")
+    if x2.stride(1) != 1 or wc.stride(1) != 1 or xs2.stride(1) != 1 or ws.stride(1) != 1:
+        raise ValueError("linear_mxfp4: operands must be K-contiguous")
+    if (x2.data_ptr() % 16 or wc.data_ptr() % 16 or (M > 1 and x2.stride(0) % 16)
+            or (N > 1 and wc.stride(0) % 16)):
+        raise ValueError("linear_mxfp4: code rows must be 16-byte aligned")
+    if (xs2.data_ptr() % 8 or ws.data_ptr() % 8 or (M > 1 and xs2.stride(0) % 8)
+            or (N > 1 and ws.stride(0) % 8)):
+        raise ValueError("linear_mxfp4: scale rows must be 8-byte aligned")
+    if out is None:
+        out = torch.empty(*lead, N, dtype=out_dtype, device=xc.device)
+    elif out.dtype not in (torch.bfloat16, torch.float32) or not out.is_contiguous() \
+            or out.numel() != M * N or out.data_ptr() % 16:
+        raise ValueError("linear_mxfp4: out must be contiguous, 16-byte aligned bf16/fp32 "
+                         "[..., N]")
+    epi = ACTS[act]
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or bias.numel() != N:
+            raise ValueError("linear_mxfp4: bias must be bf16 [N]")
+        bias = bias.contiguous()
+        if bias.data_ptr() % 16:
+            bias = bias.clone()
+        epi |= EPI_BIAS
+    r2 = None
+    if residual is not None:
+        r2 = residual.reshape(M, N)
+        if r2.dtype != torch.bfloat16 or r2.stride(1) != 1 or r2.stride(0) % 8 \
+                or r2.data_ptr() % 16:
+            r2 = r2.to(torch.bfloat16).contiguous()
+        epi |= EPI_RESIDUAL
+    rc = _lib.lib().dlbb_gemm_mxfp4_nt(
+        x2.data_ptr(), x2.stride(0) if M > 1 else K // 2, xs2.data_ptr(),
+        xs2.stride(0) if M > 1 else K // BLOCK, wc.data_ptr(),
+        wc.stride(0) if N > 1 else K // 2, ws.data_ptr(), ws.stride(0) if N > 1 else K // BLOCK,
+        out.data_ptr(), N, M, N, K, _lib.ptr(bias), _lib.ptr(r2),
+        r2.stride(0) if r2 is not None else 0, epi, 1 if out.dtype == torch.float32 else 0,
+        _lib.stream(xc.device))
+    if rc == _HIP_INVALID_VALUE:
+        raise ValueError(f"linear_mxfp4: refused by the kernel's entry point ({_MX_CONTRACT})")
+    check(rc, "gemm_mxfp4_nt")
+    CALLS[(M, N, K)] = CALLS.get((M, N, K), 0) + 1
+    return out
+
+
+def mxfp4_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                 act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
+                 out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
+                 kernels: Optional[str] = None) -> torch.Tensor:
+    """``act(x @ w.T + bias) + residual`` through the MXFP4 GEMM: ``x [..., K]`` is quantised on
+    every call (:func:`quantize_rows_mxfp4`), the bf16 weight ``w [N, K]`` once
+    (:func:`quantize_weight_mxfp4`, the cache entry :func:`w4_linear` uses)."""
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16
+    if w.shape[1] != x.shape[-1]:
+        raise ValueError(f"mxfp4_linear: x[..., {x.shape[-1]}] vs w{tuple(w.shape)}")
+    if _want_hip(kernels, x, w):            # refuse before the quantiser launches anything
+        M = x.numel() // max(x.shape[-1], 1)
+        why = gemm_contract_error(M, w.shape[0], x.shape[-1])
+        if why:
+            raise ValueError(f"mxfp4_linear: {why} ({_MX_CONTRACT})")
+    wc, ws = quantize_weight_mxfp4(w)
+    xc, xs = quantize_rows_mxfp4(x, kernels=kernels)
+    return linear_mxfp4(xc, xs, wc, ws, bias, act, residual, out_dtype, out, kernels=kernels)
+
+
+def kernel_mix() -> dict:
+    """MXFP4 GEMM launches since import and the distinct (M, N, K) they ran at."""
+    return {"calls": int(sum(CALLS.values())),
+            "shapes": [list(k) for k in sorted(CALLS)]}

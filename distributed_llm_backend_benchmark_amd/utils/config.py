@@ -200,6 +200,20 @@ def check_fp8_shapes(config: Dict[str, Any], world: int) -> None:
                               f"a multiple of 128, got {width} / {world}")
 
 
+def check_mxfp4_gemm_shapes(config: Dict[str, Any], world: int) -> None:
+    """The MXFP4 GEMM (``ops.mxfp4_linear``) reduces over K-tiles of 256: the hidden size and the
+    per-rank shard widths ``hidden_size / world`` and ``ffn_intermediate / world`` must be
+    multiples of 256 (13B at 8 ranks, 5120 / 8 = 640, is refused). Not called by
+    ``validate_config``: ``execution.gemm_dtype`` does not offer ``mxfp4``."""
+    m = config["model"]
+    for key in ("hidden_size", "ffn_intermediate"):
+        width = int(m[key])
+        if width % 256 or width % world or (width // world) % 256:
+            raise ConfigError(f"the MXFP4 GEMM needs model.{key} and model.{key} / {world} ranks "
+                              f"to be multiples of 256, got {width} / {world} = "
+                              f"{width / world:g}")
+
+
 def check_w8_shapes(config: Dict[str, Any], world: int) -> None:
     """The weight-only FP8 skinny GEMM of the decode steps reduces over units of 64 and writes
     tiles of 16 output columns: the hidden size (the column-parallel reductions) and the per-rank

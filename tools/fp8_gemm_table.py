@@ -11,9 +11,16 @@ operands (CDNA guide §5.4 rules 24/25). Per shape, best of the rounds:
 * ``torch._scaled_mm`` with row-wise e4m3fn scales, where this torch / hipBLASLt accepts it (a
   yardstick only: it is on no model path).
 
+``--mxfp4`` adds, per shape inside its contract (K % 256 == 0), the MXFP4 x MXFP4 GEMM alone
+(``mxfp4``: ``dlbb_gemm_mxfp4_nt`` on pre-quantised operands), its activation quantiser
+(``quant_mxfp4``), the ratios to ``fp8`` and to the best bf16 candidate with and without the
+quantiser, and ``spread``: (slowest - fastest round) / fastest round of ``mxfp4``, ``fp8`` and the
+best bf16 candidate, the run-to-run range inside this process. Use ``--iters`` of a few hundred with
+it, so that a timed window is tens of milliseconds.
+
 One JSON line per shape (``--out`` also appends them to a file).
 
-    python tools/fp8_gemm_table.py [--model 7B] [--ps 1,2,4,8] [--rounds 5] [--out FILE]
+    python tools/fp8_gemm_table.py [--model 7B] [--ps 1,2,4,8] [--rounds 5] [--mxfp4] [--out FILE]
 """
 import argparse
 import json
@@ -64,6 +71,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--shapes", default=None, help="comma list of case names to keep")
+    ap.add_argument("--mxfp4", action="store_true", help="add the MXFP4 GEMM and its quantiser")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     shapes = []
@@ -99,19 +107,35 @@ def main():
         ops.quantize_rows(x, out_q=qbuf, out_scale=sbuf)          # checks the contract once
         qargs = (x.data_ptr(), x.stride(0), qbuf.data_ptr(), K, sbuf.data_ptr(), M, K, stream)
         cands["quant"] = lambda: _lib.check(lib.dlbb_quant_fp8_rows(*qargs), "quant_fp8_rows")
+        mx4 = args.mxfp4 and K % 256 == 0 and M % 8 == 0 and N % 64 == 0
+        if mx4:
+            xc, xcs = ops.quantize_rows_mxfp4(x)
+            wc, wcs = ops.quantize_rows_mxfp4(w)
+            ops.linear_mxfp4(xc, xcs, wc, wcs, out=out)              # checks the contract once
+            margs = (xc.data_ptr(), K // 2, xcs.data_ptr(), K // 32, wc.data_ptr(), K // 2,
+                     wcs.data_ptr(), K // 32, out.data_ptr(), N, M, N, K, None, None, 0, 0, 0,
+                     stream)
+            cands["mxfp4"] = lambda: _lib.check(lib.dlbb_gemm_mxfp4_nt(*margs), "gemm_mxfp4_nt")
+            cbuf, csbuf = torch.empty_like(xc), torch.empty_like(xcs)
+            q4args = (x.data_ptr(), x.stride(0), cbuf.data_ptr(), K // 2, csbuf.data_ptr(),
+                      K // 32, M, K, stream)
+            cands["quant_mxfp4"] = lambda: _lib.check(lib.dlbb_quant_mxfp4_rows(*q4args),
+                                                      "quant_mxfp4_rows")
         smm = scaled_mm_candidate(xq, xs, wq, ws)
         if callable(smm):
             cands["scaled_mm"] = smm
         errs = {}
-        for n in list(bf16_names) + ["fp8", "scaled_mm"]:
+        for n in list(bf16_names) + ["fp8", "scaled_mm", "mxfp4"]:
             if n in cands:
                 y = cands[n]()
                 y = out if y is None else y
                 errs[n] = round(float((y.float() - ref).norm() / ref.norm()), 5)
         best = {n: 1e9 for n in cands}
+        worst = {n: 0.0 for n in cands}
         for _ in range(args.rounds):
             for n, fn in cands.items():
-                best[n] = min(best[n], timed(fn, args.iters))
+                t = timed(fn, args.iters)
+                best[n], worst[n] = min(best[n], t), max(worst[n], t)
         fp8.set_bal(2)
         fl = 2.0 * M * N * K
         bf16_best = min(bf16_names, key=lambda n: best[n])
@@ -125,6 +149,18 @@ def main():
                "quant_GBps": round((M * K * 3 + M * 4) / best["quant"] / 1e9, 1),
                "scaled_mm": "timed" if callable(smm) else smm,
                "rel_frobenius_err": errs}
+        if mx4:
+            rec.update({
+                "mxfp4_tflops": round(fl / best["mxfp4"] / 1e12, 1),
+                "mxfp4_vs_fp8": round(best["fp8"] / best["mxfp4"], 3),
+                "mxfp4_vs_bf16_best": round(best[bf16_best] / best["mxfp4"], 3),
+                "mxfp4_plus_quant_vs_fp8_plus_quant": round(
+                    (best["fp8"] + best["quant"]) / (best["mxfp4"] + best["quant_mxfp4"]), 3),
+                "mxfp4_plus_quant_vs_bf16_best": round(
+                    best[bf16_best] / (best["mxfp4"] + best["quant_mxfp4"]), 3),
+                "spread": {n: round(worst[n] / best[n] - 1, 4)
+                           for n in ("mxfp4", "fp8", bf16_best)},
+                "iters": args.iters, "rounds": args.rounds})
         line = json.dumps(rec)
         print(line, flush=True)
         if args.out:
