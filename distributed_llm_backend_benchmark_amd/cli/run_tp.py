@@ -33,6 +33,11 @@ sequence_length]``; needs decode tokens and a real attention, composes with ``--
 ``--decode-weights``. The split grid is bounded by ``max + N``, the ``decode`` section carries
 ``prompt_lengths`` and counts the K / V bytes of the per-row lengths, the suffix ``_ragged`` comes
 last. The captured step replays as before: the lengths are device memory.
+``--prefill-chunk C`` (``execution.prefill_chunk``) prefills the prompt in blocks of ``C`` tokens,
+each attending the KV cache filled so far (``LLM.prefill``, ``ops.prefill_attention``). Needs decode
+tokens, attention ``sdpa`` or ``flash`` and a bf16 KV cache; composes with ``--prompt-lens``,
+``--kv-page-size`` and ``--decode-weights``. The suffix ``_chunk<C>`` comes last; the ``decode``
+section carries ``prefill_chunk`` and ``prefill_ms`` (the mean prefill forward).
 ``--kv-page-size P`` (``execution.kv_page_size``; 16 | 32 | 64 | 128 | 256) keeps the K / V of those
 steps in a PAGED cache (``ops.decode``): one pool of ``--kv-pages N`` (``execution.kv_pool_pages``;
 default ``sum_b ceil((len_b + N) / P)``, exactly what the run needs) pages per layer, shared by the
@@ -112,6 +117,12 @@ def parse_args(argv=None):
                          "one at a time over a per-rank KV cache (execution.decode_tokens; 0 = "
                          "the prefill forward alone); adds a \"decode\" section to the record "
                          "and the suffix _decode<N> to the output file")
+    ap.add_argument("--prefill-chunk", type=int, default=None, metavar="C",
+                    help="with --decode: prefill the prompt in blocks of C tokens, each attending "
+                         "the KV cache filled so far (execution.prefill_chunk); needs attention "
+                         "sdpa|flash and a bf16 KV cache; composes with --prompt-lens, "
+                         "--kv-page-size and --decode-weights; output file gets the suffix "
+                         "_chunk<C> (last)")
     ap.add_argument("--decode-weights", choices=["bf16", "fp8", "mxfp4"], default=None,
                     help="with --decode: weight type the decode steps stream "
                          "(execution.decode_weight_dtype): fp8 = e4m3 with per-output-row scales "
@@ -243,6 +254,24 @@ def main(argv=None) -> int:
                 print(f"ERROR: --prompt-lens (execution.prompt_lengths) needs {why}")
             return 1
         lens = [int(v) for v in lens]
+    if args.prefill_chunk is not None:
+        ex["prefill_chunk"] = args.prefill_chunk
+    pchunk = ex.get("prefill_chunk")
+    if pchunk is not None:
+        # refused before any process group exists, like --prompt-lens
+        why = None
+        if not isinstance(pchunk, int) or pchunk < 1:
+            why = f"C >= 1, got {pchunk!r}"
+        elif not n_dec:
+            why = "decode tokens (--decode N): only the decode steps keep a KV cache"
+        elif ex.get("attention", "slice") == "slice":
+            why = "attention sdpa or flash: attention slice keeps no K / V to attend"
+        elif ex.get("kv_cache_dtype", "bf16") != "bf16":
+            why = "a bf16 KV cache (kv_cache_dtype): the chunked prefill reads bf16 rows only"
+        if why:
+            if os.environ.get("RANK", "0") == "0":
+                print(f"ERROR: --prefill-chunk (execution.prefill_chunk) needs {why}")
+            return 1
     max_len = int(args.max_len) if args.max_len else prompt + n_dec
     if n_dec and max_len < prompt + n_dec:
         print(f"ERROR: --max-len {max_len} < sequence_length {prompt} + {n_dec} decoded tokens")
@@ -405,6 +434,8 @@ def main(argv=None) -> int:
     def forward(x):
         if cache is None:
             return model(x)
+        if pchunk is not None:
+            return model.prefill(x, cache, pchunk, prompt_lens=lens)
         return model(x, kv_cache=cache, prompt_lens=lens)
 
     fwd_bytes = 0
@@ -585,6 +616,8 @@ def main(argv=None) -> int:
         }
         if dec is not None:
             results["decode"] = dec.record()
+            results["decode"]["prefill_chunk"] = pchunk
+            results["decode"]["prefill_ms"] = 1e3 * (extra["forward_device_mean"] or fwd)
         print_summary(summary, args.backend.upper(), rank)
         print(f"\nRank Statistics:\n  Variance across ranks: {rs['variance_across_ranks']:.6g}"
               f"\n  Coefficient of variation: {rs['coefficient_of_variation']:.4f}"
@@ -598,7 +631,7 @@ def main(argv=None) -> int:
         if dec is not None:                    # never overwrites the prefill record
             suffix += f"_decode{n_dec}" + ("_w8" if w8 else "_w4" if w4 else "") + \
                 ("_kv8" if kv8 else "") + ("_ragged" if lens else "") + \
-                (f"_paged{page}" if page else "")
+                (f"_paged{page}" if page else "") + (f"_chunk{pchunk}" if pchunk else "")
             d = results["decode"]
             print(f"  decode: {d['ms_per_token_mean']:.4f} ms/token ({d['timing_mode']}, "
                   f"attention {d['attention_path']}), {d['decode_tokens_per_s']:.0f} tokens/s, "

@@ -124,19 +124,6 @@ struct KvAppendArgs {
   int n_pages, psh;      // P = 1 << psh
 };
 
-// row of a pool [n_pages, H, P, D] that holds logical position `pos` of head h in page pg
-__device__ __forceinline__ int64_t pool_row(int pg, int H, int h, int psh, int64_t pos) {
-  return ((static_cast<int64_t>(pg) * H + h) << psh) + (pos & ((1 << psh) - 1));
-}
-
-// the pool row of logical position `pos` of (b, h), -1 when its page is not mapped
-__device__ __forceinline__ int64_t paged_row(const int* table, int64_t tstride, int n_pages,
-                                             int psh, int H, int b, int h, int64_t pos) {
-  const int pg = table[b * tstride + (pos >> psh)];
-  if (pg < 0 || pg >= n_pages) return -1;
-  return pool_row(pg, H, h, psh, pos);
-}
-
 // one 16-byte vector per thread step: (b, t, k|v, h, piece). PerSeq: length[b], not *length.
 // Paged: the destination row comes through the block table, an unmapped one is dropped
 template <bool PerSeq, bool Paged>

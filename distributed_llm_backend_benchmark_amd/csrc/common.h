@@ -222,6 +222,21 @@ __device__ __forceinline__ void stamp_write(uint64_t* recs, uint64_t t0) {
   r[3] = blockIdx.x | (static_cast<uint64_t>(blockIdx.y) << 32);
 }
 
+// Paged KV cache addressing (attn_decode.hip, attn_prefill.hip): pools [n_pages, H, P, D],
+// P = 1 << psh, reached through a block table int32[B, tstride].
+// row of a pool [n_pages, H, P, D] that holds logical position `pos` of head h in page pg
+__device__ __forceinline__ int64_t pool_row(int pg, int H, int h, int psh, int64_t pos) {
+  return ((static_cast<int64_t>(pg) * H + h) << psh) + (pos & ((1 << psh) - 1));
+}
+
+// the pool row of logical position `pos` of (b, h), -1 when its page is not mapped
+__device__ __forceinline__ int64_t paged_row(const int* table, int64_t tstride, int n_pages,
+                                             int psh, int H, int b, int h, int64_t pos) {
+  const int pg = table[b * tstride + (pos >> psh)];
+  if (pg < 0 || pg >= n_pages) return -1;
+  return pool_row(pg, H, h, psh, pos);
+}
+
 // Grid size for memory-bound grid-stride kernels: enough blocks to fill 256 CUs several
 // times over, capped (CDNA guide, Guideline 11).
 inline int stream_grid(int64_t work_items, int block) {

@@ -143,6 +143,8 @@ class TransformerBlock(nn.Module):
         # the row scales of an FP8 cache (None for bf16): handed through as they are
         ks, vs = cache.k_scale[layer], cache.v_scale[layer]
         hip = self.attention == "flash" and self.kernels != "torch"
+        if cache.extending:
+            return self._attn_extend(qkv, heads, cache, k, v, hip)
         if cache.paged:
             table = dict(block_table=cache.block_table, table_host=cache.table_host,
                          max_len=cache.max_len)
@@ -179,6 +181,35 @@ class TransformerBlock(nn.Module):
         else:
             dec.torch_kv_append(qkv, heads, k, v, cache.pos, ks, vs)
         return self._attn(qkv)
+
+    def _attn_extend(self, qkv, heads: int, cache, k, v, hip: bool) -> torch.Tensor:
+        """A block of ``T`` tokens over a cache that already holds tokens (``LLM.forward(...,
+        extend=True)``): the block's K / V are appended at each live row's length, then its
+        queries attend the cache under the bottom-right causal mask (``ops.prefill_attention``;
+        the torch forms for ``sdpa`` / ``kernels="torch"``). A chunk of a right-padded batch
+        (``cache.n_keep`` set) leaves the rows whose prompt has ended on pages that are unmapped
+        on purpose, and the model reserved the others itself: the ops' host checks are skipped."""
+        from ..ops import decode as dec
+
+        if cache.paged:
+            if hip:
+                table = dict(block_table=cache.block_table, table_host=cache.table_host,
+                             max_len=cache.max_len)
+                pos = cache.pos if cache.n_keep is None else None
+                ops.kv_append(qkv, heads, k, v, cache.length, pos=pos, **table)
+                return ops.prefill_attention(qkv, heads, k, v, cache.length, pos=pos, **table)
+            tab = cache.table_host.tolist()
+            dec.torch_kv_append_paged(qkv, heads, k, v, tab, cache.pos, None, None, cache.max_len)
+            return dec.torch_prefill_attention_paged(qkv, heads, k, v, tab, cache.pos,
+                                                     cache.max_len)
+        if hip:
+            ops.kv_append(qkv, heads, k, v, cache.length, pos=cache.pos)
+            return ops.prefill_attention(qkv, heads, k, v, cache.length, pos=cache.pos)
+        if cache.per_sequence:
+            dec.torch_kv_append_seq(qkv, heads, k, v, cache.pos)
+            return dec.torch_prefill_attention_seq(qkv, heads, k, v, cache.pos)
+        dec.torch_kv_append(qkv, heads, k, v, cache.pos)
+        return dec.torch_prefill_attention(qkv, heads, k, v, cache.pos)
 
     def forward(self, y1: torch.Tensor, h: torch.Tensor):
         """``y1`` = LN1(h) (computed by the caller's fused add+LN); returns (d, h) where the
@@ -305,7 +336,8 @@ class LLM(nn.Module):
             return 1
         return n
 
-    def forward(self, x: torch.Tensor, kv_cache=None, prompt_lens=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, kv_cache=None, prompt_lens=None,
+                extend: bool = False) -> torch.Tensor:
         """With ``kv_cache`` (:meth:`new_kv_cache`) and ``x [B, T, H]`` every block appends its
         K / V: ``T > 1`` on an empty cache is the prefill, ``T == 1`` a decode step over the
         cached tokens; ``T > 1`` on a non-empty cache raises ``ValueError`` (no chunked
@@ -332,6 +364,14 @@ class LLM(nn.Module):
         ``length[b]`` and is overwritten as the row grows. ``kv_cache.slot(b)`` is then a batch-1
         paged view.
 
+        ``extend=True`` (chunked prefill, see :meth:`prefill`): a block of ``T`` tokens on a cache
+        that already holds tokens is appended at each live row's length and attends the cache under
+        the bottom-right causal mask (``ops.prefill_attention``), then ``advance(T)``; on an empty
+        cache it is the ordinary prefill. bf16 KV caches only: an FP8 one raises before any launch.
+        ``prompt_lens`` then means the REAL tokens of this block per row, in ``[0, T]`` (a chunk of
+        a right-padded batch): a paged cache reserves ``pos + prompt_lens[b]`` only, and every
+        live row still moves by ``T``, so all rows stay at one position.
+
         Without a cache — plain: one pass, each all-reduce inline. Overlapped (``overlap_chunks`` = n > 1): the
         batch is split into n micro-batches run round-robin, each advancing to its next
         all-reduce; the all-reduce goes to a side comm stream (normal priority: a high-priority one stretches
@@ -347,20 +387,29 @@ class LLM(nn.Module):
                 if not kv_cache.per_sequence:
                     raise ValueError("prompt_lens needs a per_sequence=True KV cache")
                 prompt_lens = [int(v) for v in prompt_lens]
-                if T == 1 or len(prompt_lens) != x.shape[0] \
-                        or any(not 1 <= v <= T for v in prompt_lens):
-                    raise ValueError(f"prompt_lens {prompt_lens}: need {x.shape[0]} values in "
-                                     f"[1, {T}] with a prefill of T > 1 tokens")
-            if T > 1 and (any(p > 0 for p in kv_cache.pos) if kv_cache.per_sequence
-                          else kv_cache.pos != 0):
+            held = (any(p > 0 for p in kv_cache.pos) if kv_cache.per_sequence
+                    else kv_cache.pos != 0)
+            if T > 1 and held and not extend:
                 raise ValueError(f"prefill of {T} tokens on a cache holding {kv_cache.pos}: "
-                                 "chunked prefill is not supported")
+                                 "chunked prefill is not supported without extend=True")
+            extend = bool(extend) and held
+            if extend and kv_cache.kv_dtype != "bf16":
+                raise ValueError("extend=True (chunked prefill) needs kv_cache_dtype='bf16', got "
+                                 f"{kv_cache.kv_dtype!r}")
+            if prompt_lens is not None:
+                lo = 0 if extend else 1
+                if (T == 1 and not extend) or len(prompt_lens) != x.shape[0] \
+                        or any(not lo <= v <= T for v in prompt_lens):
+                    raise ValueError(f"prompt_lens {prompt_lens}: need {x.shape[0]} values in "
+                                     f"[{lo}, {T}] with a prefill of T > 1 tokens")
             kv_cache.check_room(T)
             if kv_cache.paged:
                 keep = prompt_lens if prompt_lens is not None else [T] * x.shape[0]
-                kv_cache.reserve_all([min(max(p, 0) + n, kv_cache.max_len)
+                # a row with no real token in this block keeps the pages it has
+                kv_cache.reserve_all([min(max(p, 0) + n, kv_cache.max_len) if n else 0
                                       for p, n in zip(kv_cache.pos, keep)])
                 kv_cache.n_keep = prompt_lens
+            kv_cache.extending = extend
         n = 1 if kv_cache is not None else self.overlap_split(x)
         if n == 1:
             gen = self._micro_batch(x, cache=kv_cache)
@@ -369,14 +418,21 @@ class LLM(nn.Module):
                     next(gen)
             except StopIteration as e:
                 if kv_cache is not None:
-                    kv_cache.n_keep = None
-                    if prompt_lens is not None:
+                    kv_cache.n_keep, kv_cache.extending = None, False
+                    if extend and prompt_lens is not None:
+                        # a padded chunk: every live row moves by T, no page is mapped for it
+                        kv_cache.set_lengths([p + x.shape[1] if p >= 0 else -1
+                                              for p in kv_cache.pos], reserve=False)
+                    elif prompt_lens is not None:
                         # empty slots stay empty: their rows of the padded batch are not kept
                         kv_cache.set_lengths([n if p >= 0 else -1
                                               for n, p in zip(prompt_lens, kv_cache.pos)])
                     else:
                         kv_cache.advance(x.shape[1])
                 return e.value
+            finally:
+                if kv_cache is not None:        # also when a launch raised (a failed capture)
+                    kv_cache.n_keep, kv_cache.extending = None, False
         stream = None
         cur = torch.cuda.current_stream(x.device) if x.is_cuda else None
         work = [cur] * n                        # the stream each micro-batch computes on
@@ -417,6 +473,45 @@ class LLM(nn.Module):
                 if s is not cur:
                     cur.wait_stream(s)
         return torch.cat(outs, 0)
+
+    def prefill(self, x: torch.Tensor, kv_cache, chunk: int, prompt_lens=None) -> torch.Tensor:
+        """The prompt ``x [B, S, H]`` through the model in blocks of ``chunk`` tokens, so the
+        activations are those of ``chunk`` tokens; returns the concatenated outputs ``[B, S,
+        H]``. The first block is the ordinary prefill, the later ones ``forward(..., extend=True)``.
+        ``prompt_lens`` (a right-padded batch on a per-sequence or paged cache): every block
+        starts at one position for all rows; block ``[start, start + T)`` keeps
+        ``clamp(prompt_lens[b] - start, 0, T)`` tokens of row ``b`` (a paged cache holds pages for
+        ``min(prompt_lens[b], start + T)`` positions) and the cache ends at
+        ``set_lengths(prompt_lens)``: the padding is dropped on unmapped pages and never read
+        below a row's final length."""
+        chunk, S = int(chunk), x.shape[1]
+        if chunk < 1:
+            raise ValueError(f"prefill chunk must be >= 1, got {chunk}")
+        if kv_cache.kv_dtype != "bf16" and S > chunk:
+            raise ValueError("chunked prefill needs kv_cache_dtype='bf16', got "
+                             f"{kv_cache.kv_dtype!r}")
+        if prompt_lens is not None:
+            prompt_lens = [int(v) for v in prompt_lens]
+            if not kv_cache.per_sequence or len(prompt_lens) != x.shape[0] \
+                    or any(not 1 <= v <= S for v in prompt_lens):
+                raise ValueError(f"prompt_lens {prompt_lens}: need a per_sequence=True KV cache "
+                                 f"and {x.shape[0]} values in [1, {S}]")
+        outs = []
+        for start in range(0, S, chunk):
+            xc = x[:, start:start + chunk]
+            T = xc.shape[1]
+            keep = None if prompt_lens is None else \
+                [min(max(n - start, 0), T) for n in prompt_lens]
+            if start or keep is None or T == 1:     # T == 1 at 0: a decode step, all rows real
+                outs.append(self.forward(xc, kv_cache, prompt_lens=keep if start else None,
+                                         extend=start > 0 or keep is None))
+                continue
+            outs.append(self.forward(xc, kv_cache, prompt_lens=keep))
+            kv_cache.set_lengths([T if p >= 0 else -1 for p in kv_cache.pos], reserve=False)
+        if prompt_lens is not None:
+            kv_cache.set_lengths([n if p >= 0 else -1
+                                  for n, p in zip(prompt_lens, kv_cache.pos)])
+        return torch.cat(outs, 1)
 
     @torch.no_grad()
     def load_from_dense(self, dense_state: Dict[str, torch.Tensor]) -> None:

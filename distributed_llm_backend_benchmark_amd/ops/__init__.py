@@ -12,7 +12,8 @@
 * :mod:`.clip` — global gradient-norm clipping: bucket sum-of-squares, device-side coefficient.
 * :mod:`.xent` — fused softmax cross-entropy on bf16 logits; LM-head-fused linear + loss.
 * :mod:`.decode` — KV cache (bf16, or opt-in e4m3 codes with one fp32 scale per row), append, and
-  single-query (decode) attention split over the keys.
+  single-query (decode) attention split over the keys; chunked prefill (``prefill_attention``):
+  causal attention of a block of new tokens over the cache.
 * :mod:`.embedding` — token + position embedding, backward accumulating in place (sinks).
 * :mod:`._lib` — loader; ``available()``, ``loaded_path()``.
 """
@@ -30,10 +31,10 @@ from .optim import FlatAdamW
 from .clip import GradClipper, grad_sumsq, clip_coef, sumsq_plan
 from .xent import cross_entropy, linear_cross_entropy
 from .attention import causal_attention
-from .decode import KVCache, kv_append, decode_attention, CHUNK, CHUNK_FP8, PAGE_SIZE, PAGE_SIZES
+from .decode import KVCache, kv_append, decode_attention, prefill_attention, CHUNK, CHUNK_FP8, PAGE_SIZE, PAGE_SIZES
 from .embedding import embedding
 
-__all__ = ["KVCache", "kv_append", "decode_attention", "CHUNK", "CHUNK_FP8", "PAGE_SIZE", "PAGE_SIZES", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
+__all__ = ["KVCache", "kv_append", "decode_attention", "prefill_attention", "CHUNK", "CHUNK_FP8", "PAGE_SIZE", "PAGE_SIZES", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
            "ChunkTable", "ScaleTable", "flatten_into", "linear", "layernorm", "bias_gelu",
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
            "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES",

@@ -200,6 +200,16 @@ _SIGS = {
                                            c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                            c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                            c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    # chunked prefill over the cache (csrc/attn_prefill.hip); paged: the table after `length`
+    "dlbb_attn_prefill": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_int64, c_int, c_int, c_int, c_int, c_int, c_float,
+                                  c_void_p]),
+    "dlbb_attn_prefill_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int64, c_int, c_int, c_int, c_int, c_int, c_float,
+                                      c_void_p]),
+    "dlbb_attn_prefill_paged": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
+                                        c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "dlbb_rccl_unique_id_bytes": (c_int, []),
     "dlbb_rccl_get_unique_id": (c_int, [c_void_p]),
     "dlbb_rccl_init": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

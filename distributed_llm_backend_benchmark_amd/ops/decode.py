@@ -1,4 +1,5 @@
-"""KV cache and single-query (decode) attention (``csrc/attn_decode.hip``).
+"""KV cache, single-query (decode) attention (``csrc/attn_decode.hip``) and chunked prefill
+attention (``csrc/attn_prefill.hip``).
 
 Layout, per layer and per rank: ``k_cache`` / ``v_cache`` are ``[B, H_local, L_max, D]`` bf16,
 contiguous (the key stream of one ``(b, h)`` is one contiguous run). ``length`` is ONE device
@@ -96,6 +97,13 @@ kernel templates with the row address taken through a block table). The contract
 * Torch forms: the row's mapped pages are gathered into a contiguous batch-1 cache, the
   contiguous torch form runs on it and the written pages are copied back, so the torch path is
   bit-identical to the contiguous torch path too.
+
+Chunked prefill (:func:`prefill_attention`, ``csrc/attn_prefill.hip``): a block of ``T`` tokens
+whose K / V :func:`kv_append` has just written at ``[length, length + T)`` attends the cache under
+the bottom-right causal mask (query ``i`` sees positions ``0 .. length + i``), before ``length``
+is advanced. The shared-length, per-sequence and paged forms follow the rules above (an empty slot
+gives zero rows, a key on an unmapped page is masked and never addressed, and a paged row has the
+bits of the per-sequence launch on equal contents). bf16 caches only.
 """
 
 from __future__ import annotations
@@ -238,6 +246,9 @@ class KVCache:
         # paged, during a right-padded prefill: the tokens per row that must land on mapped
         # pages (kv_append's n_keep); set and cleared by the model around that one forward
         self.n_keep: Optional[List[int]] = None
+        # True while the model runs a block over a cache that already holds tokens (chunked
+        # prefill, ``LLM.forward(..., extend=True)``); set and cleared around that forward too
+        self.extending = False
         if page_size is None and n_pages is not None:
             raise ValueError("KVCache n_pages needs a page_size")
         if page_size is not None:
@@ -374,16 +385,18 @@ class KVCache:
         if not self.per_sequence:
             raise ValueError(f"KVCache.{what} needs a per_sequence=True cache")
 
-    def set_lengths(self, lengths: Sequence[int]) -> None:
+    def set_lengths(self, lengths: Sequence[int], reserve: bool = True) -> None:
         """Set every row's device length and host mirror; a negative entry empties the slot.
         The values are staged in a device tensor that the same values reuse, so a call repeated
-        under HIP-graph capture (after an eager call with these values) is a device copy."""
+        under HIP-graph capture (after an eager call with these values) is a device copy.
+        ``reserve=False`` (paged) leaves the table as it is: the chunked prefill of a padded
+        batch parks a row whose prompt has ended past its mapped pages."""
         self._need_per_sequence("set_lengths")
         vals = [int(v) for v in lengths]
         if len(vals) != self.batch or any(v > self.max_len for v in vals):
             raise ValueError(f"KVCache lengths {vals}: need {self.batch} values <= {self.max_len}")
         vals = [max(v, -1) for v in vals]
-        if self._pages is not None:             # a negative entry gives the row's pages back
+        if self._pages is not None and reserve:  # a negative entry gives the row's pages back
             self._pages.update({self._row + b: self._pages_for(v)
                                 for b, v in enumerate(vals) if v >= 0},
                                release=[self._row + b for b, v in enumerate(vals) if v < 0])
@@ -438,6 +451,7 @@ class KVCache:
         s.n_head, s.head_dim, s.max_len = self.n_head, self.head_dim, self.max_len
         s.device = self.device
         s.page_size, s._pages, s.n_keep = self.page_size, self._pages, None
+        s.extending = False
         if self._pages is not None:
             s.per_sequence = True
             s.k, s.v, s.k_scale, s.v_scale = self.k, self.v, self.k_scale, self.v_scale
@@ -854,6 +868,127 @@ def _decode_attention_paged(qkv, n_head, k_pool, v_pool, length, len_bound, work
         raise ValueError(f"decode_attention: position {max(host)} + 1 > cache length {L_max}")
     return torch_decode_attention_paged(qkv, n_head, k_pool, v_pool, g.host(), host, k_scale,
                                         v_scale)
+
+
+def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
+                            keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Torch form of :func:`prefill_attention` at the host position ``pos``: fp32 SDPA of the
+    ``T`` queries over ``cache[:, :, :pos + T]`` (the chunk already appended) under an explicit
+    bottom-right causal mask: query ``i`` sees positions ``0 .. pos + i``. ``keep``: a boolean
+    ``[pos + T]`` key mask on top (the paged form's unmapped pages); a key it removes has its
+    K / V rows replaced by zeros, so nothing stale reaches the product."""
+    B, T, C3 = qkv.shape
+    n = min(pos + T, k_cache.shape[2])
+    q, _, _ = _views(qkv, n_head)
+    mask = torch.ones(T, n, dtype=torch.bool, device=qkv.device).tril(diagonal=pos)
+    k, v = k_cache[:, :, :n].float(), v_cache[:, :, :n].float()
+    if keep is not None:
+        mask = mask & keep[None, :n]
+        k = torch.where(keep[:n, None], k, torch.zeros_like(k))
+        v = torch.where(keep[:n, None], v, torch.zeros_like(v))
+    o = F.scaled_dot_product_attention(q.float(), k, v, attn_mask=mask)
+    return o.to(qkv.dtype).transpose(1, 2).reshape(B, T, C3 // 3)
+
+
+def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache,
+                                pos: Sequence[int]) -> torch.Tensor:
+    """Torch form of the per-sequence :func:`prefill_attention`: row ``b`` is
+    :func:`torch_prefill_attention` on its batch-1 slice at ``pos[b]``; empty slots give zero
+    rows."""
+    B, T, C3 = qkv.shape
+    out = torch.zeros(B, T, C3 // 3, dtype=qkv.dtype, device=qkv.device)
+    for b, p in enumerate(pos):
+        if p >= 0:
+            out[b:b + 1] = torch_prefill_attention(qkv[b:b + 1], n_head, k_cache[b:b + 1],
+                                                   v_cache[b:b + 1], p)
+    return out
+
+
+def torch_prefill_attention_paged(qkv, n_head: int, k_pool, v_pool,
+                                  table: Sequence[Sequence[int]], pos: Sequence[int],
+                                  max_len: Optional[int] = None) -> torch.Tensor:
+    """Torch form of the paged :func:`prefill_attention`: row ``b`` is
+    :func:`torch_prefill_attention` at ``pos[b]`` on the contiguous batch-1 gather of its pages;
+    the keys of an unmapped page are masked out (the kernel's rule); empty slots give zero
+    rows."""
+    B, T, C3 = qkv.shape
+    n_pages, P = k_pool.shape[0], k_pool.shape[2]
+    L_max = len(table[0]) * P if max_len is None else max_len
+    out = torch.zeros(B, T, C3 // 3, dtype=qkv.dtype, device=qkv.device)
+    for b, p in enumerate(pos):
+        if p < 0:
+            continue
+        n = min(p + T, L_max)
+        ids = [int(e) for e in table[b][:(n + P - 1) // P]]
+        ok = [0 <= e < n_pages for e in ids]
+        flat = [_gather_pages(t, [e if g else 0 for e, g in zip(ids, ok)])[:, :, :n]
+                for t in (k_pool, v_pool)]
+        keep = None
+        if not all(ok):
+            keep = torch.tensor(ok, device=qkv.device).repeat_interleave(P)[:n]
+        out[b:b + 1] = torch_prefill_attention(qkv[b:b + 1], n_head, flat[0], flat[1], p, keep)
+    return out
+
+
+def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor, length: torch.Tensor,
+                      pos: Union[None, int, Sequence[int]] = None,
+                      block_table: Optional[torch.Tensor] = None, table_host=None,
+                      max_len: Optional[int] = None) -> torch.Tensor:
+    """Chunked prefill (``csrc/attn_prefill.hip``): causal attention of a block of ``T`` new
+    tokens over the cache, ``qkv [B, T, 3C]`` -> ``[B, T, C]``. The block's K / V must already be
+    in the cache at ``[length, length + T)`` (:func:`kv_append`) and ``length`` not yet advanced;
+    query ``i`` of row ``b`` attends cache positions ``0 .. length_b + i`` and every key and value
+    is read from the cache. bf16 caches only.
+
+    It dispatches as :func:`kv_append` does: ``length.numel()`` 1 or ``B`` picks the shared or
+    the per-sequence form (an empty slot, ``length[b] < 0``, gives zero rows), a ``block_table``
+    the paged one (the caches are then the pools; a key on an unmapped page is masked out).
+    ``pos``: the host's copy of ``length`` for the overflow check and, paged, for the check that
+    every page of ``[0, pos_b + T)`` is mapped (None on the HIP path = no host check). GPU
+    tensors with head dim 64 / 128 take the HIP kernel; CPU tensors, ``DLBB_KERNELS=torch`` and
+    other head dims the torch forms (:func:`torch_prefill_attention`)."""
+    if qkv.dim() != 3 or qkv.shape[1] < 1:
+        raise ValueError(f"prefill_attention takes qkv [B, T >= 1, 3C], got {tuple(qkv.shape)}")
+    if k_cache.dtype == E4M3 or v_cache.dtype == E4M3:
+        raise ValueError("prefill_attention reads a bf16 KV cache only (kv_cache_dtype='bf16'), "
+                         f"got {k_cache.dtype}")
+    B, T, C3 = qkv.shape
+    C = C3 // 3
+    what = "prefill_attention"
+    g = None
+    if block_table is not None:
+        g = _Paged(what, qkv, k_cache, v_cache, length, block_table, table_host, max_len)
+        L_max, seq = g.L_max, True
+    else:
+        L_max, seq = k_cache.shape[2], _per_sequence(length, B, what)
+    host = None
+    if pos is not None:
+        host = _host_positions(length, pos) if seq else [int(pos)]
+        if max(host) + T > L_max:
+            raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
+        if g is not None:
+            g.check_mapped(host, [T] * B)
+    if use_hip(qkv) and (g.hip_ok(qkv, n_head, k_cache, v_cache, None, None) if g is not None
+                         else hip_supported(qkv, n_head, k_cache, v_cache)):
+        D = C // n_head
+        out = torch.empty(B, T, C, dtype=qkv.dtype, device=qkv.device)
+        name = "dlbb_attn_prefill" + ("_paged" if g is not None else "_seq" if seq else "")
+        table = g.args() if g is not None else ()
+        check(getattr(_lib.lib(), name)(qkv.data_ptr(), C3, k_cache.data_ptr(),
+                                        v_cache.data_ptr(), length.data_ptr(), *table,
+                                        out.data_ptr(), C, B, T, n_head, D, L_max,
+                                        1.0 / math.sqrt(D), _lib.stream(qkv.device)), name[5:])
+        return out
+    if host is None:
+        host = _host_positions(length, None) if seq else [_host_pos(length, None)]
+        if max(host) + T > L_max:
+            raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
+    if g is not None:
+        return torch_prefill_attention_paged(qkv, n_head, k_cache, v_cache, g.host(), host, L_max)
+    if seq:
+        return torch_prefill_attention_seq(qkv, n_head, k_cache, v_cache, host)
+    return torch_prefill_attention(qkv, n_head, k_cache, v_cache, host[0])
 
 
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,

@@ -46,6 +46,10 @@ Additions (all optional, defaults keep reference behaviour):
   the decode steps run over a PAGED KV cache of pages of this many positions, shared by the batch
   rows through a block table (``ops.decode``; ``run_tp --kv-page-size``). Needs ``decode_tokens``
   and a real attention.
+* ``execution.prefill_chunk``: absent (default: the prompt in one forward) | an int >= 1 — the
+  prompt is prefilled in blocks of this many tokens, each attending the KV cache filled so far
+  (``LLM.prefill``, ``ops.prefill_attention``; ``run_tp --prefill-chunk``). Needs ``decode_tokens``,
+  attention ``sdpa`` or ``flash`` and a bf16 KV cache.
 * ``execution.kv_pool_pages``: absent (default: exactly the pages the run needs) | an int >= 1 —
   the pages of that pool, per layer (``run_tp --kv-pages``). Needs ``kv_page_size``.
 """
@@ -184,6 +188,12 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
             raise ConfigError(f"execution.kv_pool_pages must be an int >= 1, got {pool!r}")
         if page is None:
             raise ConfigError("execution.kv_pool_pages needs execution.kv_page_size")
+    chunk = ex.get("prefill_chunk")             # no default: absent = one-shot prefill
+    if chunk is not None:
+        if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
+            raise ConfigError(f"execution.prefill_chunk must be an int >= 1, got {chunk!r}")
+        if ex["kv_cache_dtype"] != "bf16":
+            raise ConfigError("execution.prefill_chunk needs kv_cache_dtype bf16")
     return cfg
 
 

@@ -1,5 +1,13 @@
 """Device time of the causal attention forward / backward (ours vs torch SDPA vs the library
-backward) at the GPT-2 shape and longer sequences, head dim 64 and 128."""
+backward) at the GPT-2 shape and longer sequences, head dim 64 and 128.
+
+``--prefill [--out FILE]``: the chunked-prefill kernel (``ops.prefill_attention``) instead: a block
+of T queries over a cache that already holds ``prefix`` tokens, at the 7B head shape (H 32, D 128)
+and GPT-2's (H 12, D 64), B 1 / 8, T 512 / 2048, prefix 0 / 2048 / 8192. Per row, in one process
+and interleaved round by round: the kernel, torch SDPA under an explicit mask on the same cache, a
+copy of the K / V bytes the kernel reads and, at prefix 0, ``attn_fwd`` on the same qkv (the same
+FLOPs). One JSON line per row (default ``profiles/prefill_attention/attn_prefill.jsonl``)."""
+import argparse
 import json
 import os
 import sys
@@ -26,6 +34,65 @@ def t_best(fn, iters=20, rounds=5):
         best = min(best, s.elapsed_time(e) / iters * 1e-3)
     return best
 
+
+def prefill_rows(out_path):
+    import torch.nn.functional as F
+
+    from distributed_llm_backend_benchmark_amd.ops import kv_append, prefill_attention
+    from distributed_llm_backend_benchmark_amd.ops.attention import _views
+
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    with open(out_path, "w") as fh:
+        for H, D in ((32, 128), (12, 64)):
+            for B in (1, 8):
+                for T in (512, 2048):
+                    for prefix in (0, 2048, 8192):
+                        n = prefix + T
+                        qkv = torch.randn(B, T, 3 * H * D, device="cuda", generator=gen).bfloat16()
+                        kc = torch.randn(B, H, n, D, device="cuda", generator=gen).bfloat16()
+                        vc = torch.randn(B, H, n, D, device="cuda", generator=gen).bfloat16()
+                        length = torch.tensor([prefix], dtype=torch.int32, device="cuda")
+                        kv_append(qkv, H, kc, vc, length)
+                        mask = torch.ones(T, n, dtype=torch.bool, device="cuda").tril(prefix)
+                        q = _views(qkv, H)[0]
+                        fns = {"prefill": lambda: prefill_attention(qkv, H, kc, vc, length),
+                               "sdpa_masked": lambda: F.scaled_dot_product_attention(
+                                   q, kc, vc, attn_mask=mask),
+                               "kv_copy": lambda: (kc.clone(), vc.clone())}
+                        if prefix == 0:
+                            fns["attn_fwd"] = lambda: attn_fwd(qkv, H)
+                        err = float((fns["prefill"]().float() - fns["sdpa_masked"]().transpose(1, 2)
+                                     .reshape(B, T, H * D).float()).abs().max())
+                        best = {k: 1e9 for k in fns}
+                        for _ in range(5):                      # interleaved: one round of each
+                            for k, fn in fns.items():
+                                best[k] = min(best[k], t_best(fn, iters=10, rounds=1))
+                        fl = 4.0 * B * H * D * (T * prefix + T * (T + 1) / 2)
+                        nbytes = 2 * B * H * n * D * 2
+                        rec = {"H": H, "D": D, "B": B, "T": T, "prefix": prefix,
+                               "workgroups": -(-T // 128) * H * B,
+                               "workgroups_per_cu": -(-T // 128) * H * B / 256,
+                               "max_abs_diff_vs_sdpa": err, "kv_bytes": nbytes,
+                               "kv_copy_GBps": 2 * nbytes / best["kv_copy"] / 1e9,
+                               "tflops_prefill": fl / best["prefill"] / 1e12,
+                               "tflops_sdpa_masked": fl / best["sdpa_masked"] / 1e12}
+                        rec.update({f"us_{k}": v * 1e6 for k, v in best.items()})
+                        if prefix == 0:
+                            rec["tflops_attn_fwd"] = fl / best["attn_fwd"] / 1e12
+                        print(json.dumps(rec), flush=True)
+                        fh.write(json.dumps(rec) + "\n")
+                        fh.flush()
+
+
+_ap = argparse.ArgumentParser()
+_ap.add_argument("--prefill", action="store_true")
+_ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(
+    os.path.abspath(__file__))), "profiles", "prefill_attention", "attn_prefill.jsonl"))
+_args = _ap.parse_args()
+if _args.prefill:
+    prefill_rows(_args.out)
+    sys.exit(0)
 
 for B, T, H, D in ((16, 1024, 12, 64), (8, 2048, 12, 64), (4, 4096, 16, 64),
                    (16, 1024, 6, 128), (4, 4096, 8, 128)):
