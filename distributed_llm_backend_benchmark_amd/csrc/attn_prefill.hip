@@ -1,5 +1,5 @@
 // Chunked prefill: causal attention of a block of T new tokens over a KV cache, gfx950 (MI355X,
-// CDNA4), bf16 cache, head dim 64 / 128.
+// CDNA4), bf16 or FP8 (e4m3fn) cache, head dim 64 / 128.
 //
 // Contract. qkv is the chunk's fused activation [B, T, 3, H, D] bf16 (token row stride ld); its
 // K / V rows were appended to the cache at [len_b, len_b + T) by dlbb_kv_append* BEFORE this
@@ -13,10 +13,10 @@
 // 0 * NaN is NaN in the PV product): a tile row past kend is redirected to position kend - 1 and
 // its score masked.
 //
-// One kernel template <D, PerSeq, Paged> on attn_fwd_kernel's tile geometry (attn_tile.h): a
-// workgroup of 4 waves takes 128 queries of one (b, h), a lane owns one query (S^T = K Q^T on
+// One kernel template <D, PerSeq, Paged, Fp8> on attn_fwd_kernel's tile geometry (attn_tile.h):
+// a workgroup of 4 waves takes 128 queries of one (b, h), a lane owns one query (S^T = K Q^T on
 // v_mfma_f32_32x32x16_bf16), K / V tiles are 8-KiB images (64 keys at D = 64, 32 at D = 128)
-// staged by LDS-DMA, double buffered, read back with ds_read_b128 (K rows) and
+// staged by LDS-DMA (bf16 cache), double buffered, read back with ds_read_b128 (K rows) and
 // ds_read_b64_tr_b16 (V, transposed) under the same swizzles; the softmax keeps the deferred
 // running max. What differs from the forward:
 //   * Sources. A key tile is KB consecutive cache rows of 2 D bytes: a lane's DMA source is
@@ -47,6 +47,34 @@
 //     them. len_b is also a device value, so the host could not choose per launch. The block
 //     order is the XCD-aware one (head_block): the query blocks of a head share one L2 and read
 //     the head's prefix from HBM once.
+//
+// FP8 cache (template parameter Fp8; dlbb_attn_prefill_fp8{,_seq,_paged}). k_cache / v_cache hold
+// e4m3fn codes [B, H, L_max, D] (pools [n_pages, H, P, D]) and k_scale / v_scale one fp32 scale
+// per row [B, H, L_max] ([n_pages, H, P]), as dlbb_kv_append_fp8* wrote them: a row is
+// float(code) * scale. Every rule above holds; the chunk attends to its own rows in their
+// quantised form. The bf16 instantiations compile to the instructions they had before.
+//   * Staging. An FP8 tile cannot go global -> LDS by DMA and still be read as bf16 MFMA
+//     operands, so it goes through registers: right after the barrier that frees the other
+//     buffer each thread issues one 16-byte global load of K codes and one of V codes of tile
+//     kt + 1 (KB * D / 256 = 16 codes per operand; the threads of a row's first two runs also
+//     load its k- / v-scale), the loads fly while tile kt is computed, and before the next barrier
+//     the thread widens them and writes the SAME swizzled bf16 images with ds_write_b128. The S
+//     and PV phases keep their LDS reads, fragment layouts and mask arithmetic; the widening is
+//     paid once per workgroup (16 codes per operand per thread per tile), not by each of the four
+//     waves at read time.
+//   * Widening is exact and carries no scale (e4m3x4_to_bf16): folding the scale in would round
+//     code * scale to bf16. k_scale[key] multiplies the fp32 score before the masks and the
+//     running max, v_scale[key] the fp32 probability before it is rounded to bf16 for the PV
+//     operand; the row sum l takes the unscaled probability. The scales of a tile lie behind the
+//     four images (per buffer KB k-scales, KB v-scales) and are read as broadcast ds_read_b128:
+//     the four keys (e & 3) of a register group are consecutive positions.
+//   * Redirected rows (past kend; a dead paged group) take their SCALE from the redirected
+//     position too: a stale scale may be NaN, and 0 * NaN is NaN in the PV operand.
+//   * Tile size: FwdGeo<D>::KB is kept (4 KiB of codes per operand per tile). The images in LDS
+//     are bf16 either way, so doubling the keys per tile would double the LDS (66 KiB per
+//     workgroup) and the score registers (the D = 128 forms already take 200 VGPRs, 2 waves per
+//     SIMD) for global loads that are already a whole tile ahead of their use; keeping KB also
+//     keeps the tile walk, the masks and the paged group bits those of the bf16 kernel.
 #include "attn_tile.h"
 #include "common.h"
 
@@ -55,6 +83,9 @@ namespace dlbb {
 namespace {
 
 constexpr float kPfNegBig = -1.0e30f;   // raw score of a masked key: finite
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 struct PrefillArgs {
   const uint16_t* qkv;      // [B, T, 3, H, D], token row stride ld
@@ -68,9 +99,31 @@ struct PrefillArgs {
   const int* table;         // Paged: [B, tstride]
   int64_t tstride;
   int n_pages, psh;         // P = 1 << psh
+  const float* k_scale;     // Fp8: [B, H, L_max]; Paged: [n_pages, H, P]. The caches hold bytes
+  const float* v_scale;
 };
 
-template <int D, bool PerSeq, bool Paged>
+// 4 e4m3fn bytes (byte order) -> 4 bf16 (two words), exactly: v_cvt_pk_f32_fp8 is exact and an
+// e4m3 value has 3 mantissa bits, so the low half of its fp32 form is zero and v_perm_b32 keeps
+// the high halves. 4 VALU ops per 4 codes.
+__device__ __forceinline__ u32x2 e4m3x4_to_bf16(uint32_t w) {
+  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(w), false);
+  const auto b = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(w), true);
+  return u32x2{__builtin_amdgcn_perm(__float_as_uint(a[1]), __float_as_uint(a[0]), 0x07060302u),
+               __builtin_amdgcn_perm(__float_as_uint(b[1]), __float_as_uint(b[0]), 0x07060302u)};
+}
+
+// 16 codes -> the two 16-B chunks c0, c0 + 1 of image row `row_base` under swizzle `swz`
+__device__ __forceinline__ void widen_store(const u32x4& codes, char* row_base, int c0, int swz) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const u32x2 lo = e4m3x4_to_bf16(codes[2 * i]), hi = e4m3x4_to_bf16(codes[2 * i + 1]);
+    *reinterpret_cast<u32x4*>(row_base + (((c0 + i) ^ swz) << 4)) =
+        u32x4{lo[0], lo[1], hi[0], hi[1]};
+  }
+}
+
+template <int D, bool PerSeq, bool Paged, bool Fp8>
 __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_kernel(PrefillArgs a) {
   using G = FwdGeo<D>;
   constexpr int KB = G::KB, ROW = G::ROW, RPI = G::RPI, TILE = G::TILE;
@@ -209,20 +262,103 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_kernel(PrefillAr
     }
   };
 
-  unsigned gnext = stage(0, tileK(0), tileV(0));
+  // Fp8: a thread owns the 16-code run `frun` of tile row `frow` of K and of V (KB * D / 256 = 16
+  // codes per operand), and the threads of runs 0 / 1 the row's k- / v-scale. fetch() issues the
+  // global loads of tile k0 into registers (the row redirects and group bits are stage()'s) and
+  // spill() widens them into the images of buffer c and puts the scales behind the four images:
+  // per buffer KB k-scales, then KB v-scales. A redirected row takes its scales from the
+  // redirected position too: a stale scale may be NaN and 0 * NaN is NaN in the PV operand.
+  [[maybe_unused]] const int frow = threadIdx.x / (D / 16), frun = threadIdx.x % (D / 16);
+  [[maybe_unused]] u32x4 kreg, vreg;
+  [[maybe_unused]] float sreg = 0.f;
+  auto tileS = [&](int c) { return reinterpret_cast<float*>(smem + 4 * TILE) + c * 2 * KB; };
+  auto fetch = [&](int k0) -> unsigned {
+    int64_t rowi;                                  // cache row: codes at rowi * D, scale at rowi
+    unsigned bits = kAllGroups;
+    if constexpr (!Paged) {
+      const int pos = k0 + frow;
+      rowi = bh_row + (pos < kend ? pos : kend - 1);
+    } else {
+      int pg[NG];
+      unsigned mp = 0, um = 0;
+      int safe_pg = 0, safe_pos = 0;
+#pragma unroll
+      for (int g = NG - 1; g >= 0; --g) {
+        const int p0 = k0 + 16 * g;
+        pg[g] = -1;
+        if (p0 < kend) {
+          pg[g] = trow[p0 >> a.psh];
+          if (pg[g] >= 0 && pg[g] < a.n_pages) {
+            mp |= 1u << g;
+            safe_pg = pg[g];
+            safe_pos = p0;
+          } else {
+            um |= 1u << g;
+          }
+        }
+      }
+      if (mp == 0) return um << NG;
+      const int g = frow >> 4;
+      int pos = k0 + frow;
+      int page = pg[0];
+#pragma unroll
+      for (int j = 1; j < NG; ++j) page = g == j ? pg[j] : page;
+      const bool ok = ((mp >> g) & 1u) && pos < kend;
+      page = ok ? page : safe_pg;
+      pos = ok ? pos : safe_pos;
+      rowi = pool_row(page, a.H, h, a.psh, pos);
+      bits = mp | (um << NG);
+    }
+    const int64_t e = rowi * D + 16 * frun;
+    kreg = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(a.k_cache) + e);
+    vreg = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(a.v_cache) + e);
+    if (frun < 2) sreg = (frun ? a.v_scale : a.k_scale)[rowi];
+    return bits;
+  };
+  auto spill = [&](int c) {
+    widen_store(kreg, tileK(c) + frow * ROW, 2 * frun, kswz_d<D>(frow));
+    widen_store(vreg, tileV(c) + frow * ROW, 2 * frun, vswz_d<D>(frow));
+    if (frun < 2) tileS(c)[frun * KB + frow] = sreg;
+  };
+
+  unsigned gnext;
+  if constexpr (Fp8) {
+    gnext = fetch(0);
+    if (gnext & kAllGroups) spill(0);
+  } else {
+    gnext = stage(0, tileK(0), tileV(0));
+  }
   for (int kt = 0; kt < nt; ++kt) {
     const int cur = kt & 1;
     const unsigned gbits = gnext;
-    // one barrier per tile: it both publishes tile kt (every wave's DMA retired) and frees
-    // buffer cur^1 (every wave finished tile kt-1), so the restage goes right after it
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // one barrier per tile: it both publishes tile kt (every wave's DMA retired; Fp8: every
+    // wave's LDS writes) and frees buffer cur^1 (every wave finished tile kt-1), so the restage
+    // goes right after it. Fp8: the loads of tile kt+1 are issued here and fly while tile kt is
+    // computed; they are widened into buffer cur^1 after it
+    if constexpr (Fp8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (kt + 1 < nt) gnext = stage((kt + 1) * KB, tileK(cur ^ 1), tileV(cur ^ 1));
+    if (kt + 1 < nt) {
+      if constexpr (Fp8) gnext = fetch((kt + 1) * KB);
+      else gnext = stage((kt + 1) * KB, tileK(cur ^ 1), tileV(cur ^ 1));
+    }
     const int k0 = kt * KB;
     // wave-uniform: the wave has queries, the tile a key one of them sees, and mapped rows
     if (wave_live && k0 <= wtop && (gbits & kAllGroups)) {
       const char* tk = tileK(cur);
       const char* tv = tileV(cur);
+      // Fp8: the tile's scales, each batch read in one go ahead of its use (the k-scales under
+      // the S MFMAs, the v-scales under the exponentials) so that no multiply waits on LDS alone.
+      // The 4 keys (e & 3) of a register group are consecutive: one broadcast 16-B read
+      [[maybe_unused]] f32x4 sc[G::NKK][4];
+      [[maybe_unused]] auto read_scales = [&](const float* base) {
+#pragma unroll
+        for (int kk = 0; kk < G::NKK; ++kk)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            sc[kk][q] = *reinterpret_cast<const f32x4*>(base + kk * 32 + 8 * q + 4 * hi);
+      };
+      if constexpr (Fp8) read_scales(tileS(cur));
       // ---- S^T for the 32-key halves
       f32x16 s[G::NKK];
 #pragma unroll
@@ -237,6 +373,15 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_kernel(PrefillAr
               *reinterpret_cast<const bf16x8*>(tk + row * ROW + ((c ^ kswz_d<D>(row)) << 4));
           s[kk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[kk], 0, 0, 0);
         }
+      }
+      // Fp8: the keys' scales on the fp32 scores, before the masks (a masked key's scale may be
+      // stale); then the v-scales set off
+      if constexpr (Fp8) {
+#pragma unroll
+        for (int kk = 0; kk < G::NKK; ++kk)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) s[kk][e] *= sc[kk][e >> 2][e & 3];
+        read_scales(tileS(cur) + KB);
       }
       // ---- masks (lane = one query; keys in registers), online softmax
       if (k0 + KB - 1 > wlim) {                     // some key of the tile beyond some query
@@ -296,6 +441,10 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_kernel(PrefillAr
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
           bf16x8 pf;
+          if constexpr (Fp8) {                       // v_scale[key] on the fp32 probability
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s[kk][8 * st + j] *= sc[kk][2 * st + (j >> 2)][j & 3];
+          }
 #pragma unroll
           for (int j = 0; j < 8; ++j)
             pf[j] = __builtin_bit_cast(short, static_cast<__bf16>(s[kk][8 * st + j]));
@@ -315,6 +464,9 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_kernel(PrefillAr
             o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[dt], 0, 0, 0);
           }
         }
+    }
+    if constexpr (Fp8) {
+      if (kt + 1 < nt && (gnext & kAllGroups)) spill(cur ^ 1);
     }
   }
 
@@ -337,14 +489,17 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_kernel(PrefillAr
 bool mis(const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) & (n - 1); }
 
 // validation and the launch of the three entry points (table = null: a contiguous cache)
-template <bool PerSeq, bool Paged>
+template <bool PerSeq, bool Paged, bool Fp8 = false>
 int prefill_launch(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache,
                    const void* length, const void* table, int64_t tstride, int n_pages, int P,
                    void* out, int64_t ldo, int B, int T, int H, int D, int L_max, float scale,
-                   hipStream_t stream) {
+                   hipStream_t stream, const void* k_scale = nullptr,
+                   const void* v_scale = nullptr) {
   if (D != 64 && D != 128) return hipErrorInvalidValue;
   if (B <= 0 || T <= 0 || H <= 0 || L_max <= 0 || !(scale > 0.f)) return hipErrorInvalidValue;
   if (!qkv || !k_cache || !v_cache || !out || !length) return hipErrorInvalidValue;
+  if (Fp8 && (!k_scale || !v_scale || mis(k_scale, 4) || mis(v_scale, 4)))
+    return hipErrorInvalidValue;
   if (ld % 8 || ld < 3 * H * D || ldo % 4 || ldo < H * D) return hipErrorInvalidValue;
   if (mis(qkv, 16) || mis(k_cache, 16) || mis(v_cache, 16) || mis(out, 8) || mis(length, 4))
     return hipErrorInvalidValue;
@@ -360,14 +515,15 @@ int prefill_launch(const void* qkv, int64_t ld, const void* k_cache, const void*
                 static_cast<const uint16_t*>(v_cache), static_cast<const int*>(length),
                 static_cast<uint16_t*>(out), ld, ldo, B, T, H, L_max,
                 scale * 1.4426950408889634f, static_cast<const int*>(table), tstride, n_pages,
-                psh};
+                psh, static_cast<const float*>(k_scale), static_cast<const float*>(v_scale)};
   const dim3 grid((T + kQB - 1) / kQB, H, B);
+  // Fp8: 2 buffers x (KB k-scales + KB v-scales) behind the four images
   if (D == 64)
-    hipLaunchKernelGGL((attn_prefill_kernel<64, PerSeq, Paged>), grid, dim3(kAttnThreads),
-                       4 * FwdGeo<64>::TILE, stream, a);
+    hipLaunchKernelGGL((attn_prefill_kernel<64, PerSeq, Paged, Fp8>), grid, dim3(kAttnThreads),
+                       4 * FwdGeo<64>::TILE + (Fp8 ? 16 * FwdGeo<64>::KB : 0), stream, a);
   else
-    hipLaunchKernelGGL((attn_prefill_kernel<128, PerSeq, Paged>), grid, dim3(kAttnThreads),
-                       4 * FwdGeo<128>::TILE, stream, a);
+    hipLaunchKernelGGL((attn_prefill_kernel<128, PerSeq, Paged, Fp8>), grid, dim3(kAttnThreads),
+                       4 * FwdGeo<128>::TILE + (Fp8 ? 16 * FwdGeo<128>::KB : 0), stream, a);
   return hipGetLastError();
 }
 
@@ -411,4 +567,42 @@ DLBB_API int dlbb_attn_prefill_paged(const void* qkv, int64_t ld, const void* k_
                                      int L_max, float scale, hipStream_t stream) {
   return prefill_launch<true, true>(qkv, ld, k_pool, v_pool, length, block_table, table_stride,
                                     n_pages, P, out, ldo, B, T, H, D, L_max, scale, stream);
+}
+
+// The same over the FP8 cache (file header, "FP8 cache"): k_cache / v_cache [B, H, L_max, D]
+// e4m3fn, k_scale / v_scale [B, H, L_max] fp32, as dlbb_kv_append_fp8 wrote them. The scales must
+// be non-null and 4-byte aligned, the code pointers 16-byte aligned.
+DLBB_API int dlbb_attn_prefill_fp8(const void* qkv, int64_t ld, const void* k_cache,
+                                   const void* v_cache, const void* k_scale, const void* v_scale,
+                                   const void* length, void* out, int64_t ldo, int B, int T,
+                                   int H, int D, int L_max, float scale, hipStream_t stream) {
+  return prefill_launch<false, false, true>(qkv, ld, k_cache, v_cache, length, nullptr, 0, 0, 0,
+                                            out, ldo, B, T, H, D, L_max, scale, stream, k_scale,
+                                            v_scale);
+}
+
+// The FP8 cache with per-sequence lengths (dlbb_attn_prefill_seq's rules).
+DLBB_API int dlbb_attn_prefill_fp8_seq(const void* qkv, int64_t ld, const void* k_cache,
+                                       const void* v_cache, const void* k_scale,
+                                       const void* v_scale, const void* length, void* out,
+                                       int64_t ldo, int B, int T, int H, int D, int L_max,
+                                       float scale, hipStream_t stream) {
+  return prefill_launch<true, false, true>(qkv, ld, k_cache, v_cache, length, nullptr, 0, 0, 0,
+                                           out, ldo, B, T, H, D, L_max, scale, stream, k_scale,
+                                           v_scale);
+}
+
+// The FP8 pools (dlbb_attn_prefill_paged's rules): k_pool / v_pool [n_pages, H, P, D] e4m3fn,
+// k_scale / v_scale [n_pages, H, P] fp32. An entry outside [0, n_pages) becomes no address, for
+// codes or for scales.
+DLBB_API int dlbb_attn_prefill_fp8_paged(const void* qkv, int64_t ld, const void* k_pool,
+                                         const void* v_pool, const void* k_scale,
+                                         const void* v_scale, const void* length,
+                                         const void* block_table, int64_t table_stride,
+                                         int n_pages, int P, void* out, int64_t ldo, int B, int T,
+                                         int H, int D, int L_max, float scale,
+                                         hipStream_t stream) {
+  return prefill_launch<true, true, true>(qkv, ld, k_pool, v_pool, length, block_table,
+                                          table_stride, n_pages, P, out, ldo, B, T, H, D, L_max,
+                                          scale, stream, k_scale, v_scale);
 }

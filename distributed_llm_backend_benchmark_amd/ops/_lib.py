@@ -210,6 +210,17 @@ _SIGS = {
     "dlbb_attn_prefill_paged": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int64, c_int, c_int, c_void_p, c_int64,
                                         c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    # the same over the FP8 cache: k_scale, v_scale after the caches
+    "dlbb_attn_prefill_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                      c_int, c_float, c_void_p]),
+    "dlbb_attn_prefill_fp8_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                          c_int, c_int, c_int, c_float, c_void_p]),
+    "dlbb_attn_prefill_fp8_paged": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                            c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                            c_float, c_void_p]),
     "dlbb_rccl_unique_id_bytes": (c_int, []),
     "dlbb_rccl_get_unique_id": (c_int, [c_void_p]),
     "dlbb_rccl_init": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

@@ -103,7 +103,11 @@ whose K / V :func:`kv_append` has just written at ``[length, length + T)`` atten
 the bottom-right causal mask (query ``i`` sees positions ``0 .. length + i``), before ``length``
 is advanced. The shared-length, per-sequence and paged forms follow the rules above (an empty slot
 gives zero rows, a key on an unmapped page is masked and never addressed, and a paged row has the
-bits of the per-sequence launch on equal contents). bf16 caches only.
+bits of the per-sequence launch on equal contents). With ``k_scale`` / ``v_scale`` it reads the
+FP8 cache (the ``dlbb_attn_prefill_fp8*`` entry points): the codes are widened exactly to bf16 on
+their way into LDS, ``k_scale[key]`` multiplies the fp32 score and ``v_scale[key]`` the fp32
+probability, and the chunk attends to its own rows in the quantised form the append stored, as a
+decode step does.
 """
 
 from __future__ import annotations
@@ -871,17 +875,23 @@ def _decode_attention_paged(qkv, n_head, k_pool, v_pool, length, len_bound, work
 
 
 def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
-                            keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            keep: Optional[torch.Tensor] = None, k_scale=None,
+                            v_scale=None) -> torch.Tensor:
     """Torch form of :func:`prefill_attention` at the host position ``pos``: fp32 SDPA of the
-    ``T`` queries over ``cache[:, :, :pos + T]`` (the chunk already appended) under an explicit
-    bottom-right causal mask: query ``i`` sees positions ``0 .. pos + i``. ``keep``: a boolean
-    ``[pos + T]`` key mask on top (the paged form's unmapped pages); a key it removes has its
-    K / V rows replaced by zeros, so nothing stale reaches the product."""
+    ``T`` queries over ``cache[:, :, :pos + T]`` (the chunk already appended; an FP8 cache is
+    dequantised with :func:`dequantize`) under an explicit bottom-right causal mask: query ``i``
+    sees positions ``0 .. pos + i``. ``keep``: a boolean ``[pos + T]`` key mask on top (the paged
+    form's unmapped pages); a key it removes has its K / V rows replaced by zeros, so nothing
+    stale reaches the product."""
     B, T, C3 = qkv.shape
     n = min(pos + T, k_cache.shape[2])
     q, _, _ = _views(qkv, n_head)
     mask = torch.ones(T, n, dtype=torch.bool, device=qkv.device).tril(diagonal=pos)
-    k, v = k_cache[:, :, :n].float(), v_cache[:, :, :n].float()
+    if k_scale is None:
+        k, v = k_cache[:, :, :n].float(), v_cache[:, :, :n].float()
+    else:
+        k = dequantize(k_cache[:, :, :n], k_scale[:, :, :n])
+        v = dequantize(v_cache[:, :, :n], v_scale[:, :, :n])
     if keep is not None:
         mask = mask & keep[None, :n]
         k = torch.where(keep[:n, None], k, torch.zeros_like(k))
@@ -890,8 +900,8 @@ def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
     return o.to(qkv.dtype).transpose(1, 2).reshape(B, T, C3 // 3)
 
 
-def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache,
-                                pos: Sequence[int]) -> torch.Tensor:
+def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int],
+                                k_scale=None, v_scale=None) -> torch.Tensor:
     """Torch form of the per-sequence :func:`prefill_attention`: row ``b`` is
     :func:`torch_prefill_attention` on its batch-1 slice at ``pos[b]``; empty slots give zero
     rows."""
@@ -899,18 +909,21 @@ def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache,
     out = torch.zeros(B, T, C3 // 3, dtype=qkv.dtype, device=qkv.device)
     for b, p in enumerate(pos):
         if p >= 0:
-            out[b:b + 1] = torch_prefill_attention(qkv[b:b + 1], n_head, k_cache[b:b + 1],
-                                                   v_cache[b:b + 1], p)
+            out[b:b + 1] = torch_prefill_attention(
+                qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p, None,
+                None if k_scale is None else k_scale[b:b + 1],
+                None if v_scale is None else v_scale[b:b + 1])
     return out
 
 
 def torch_prefill_attention_paged(qkv, n_head: int, k_pool, v_pool,
                                   table: Sequence[Sequence[int]], pos: Sequence[int],
-                                  max_len: Optional[int] = None) -> torch.Tensor:
+                                  max_len: Optional[int] = None, k_scale=None,
+                                  v_scale=None) -> torch.Tensor:
     """Torch form of the paged :func:`prefill_attention`: row ``b`` is
-    :func:`torch_prefill_attention` at ``pos[b]`` on the contiguous batch-1 gather of its pages;
-    the keys of an unmapped page are masked out (the kernel's rule); empty slots give zero
-    rows."""
+    :func:`torch_prefill_attention` at ``pos[b]`` on the contiguous batch-1 gather of its pages
+    (an FP8 cache's scale pages with its code pages); the keys of an unmapped page are masked
+    out (the kernel's rule); empty slots give zero rows."""
     B, T, C3 = qkv.shape
     n_pages, P = k_pool.shape[0], k_pool.shape[2]
     L_max = len(table[0]) * P if max_len is None else max_len
@@ -922,11 +935,12 @@ def torch_prefill_attention_paged(qkv, n_head: int, k_pool, v_pool,
         ids = [int(e) for e in table[b][:(n + P - 1) // P]]
         ok = [0 <= e < n_pages for e in ids]
         flat = [_gather_pages(t, [e if g else 0 for e, g in zip(ids, ok)])[:, :, :n]
-                for t in (k_pool, v_pool)]
+                for t in (k_pool, v_pool, k_scale, v_scale) if t is not None]
         keep = None
         if not all(ok):
             keep = torch.tensor(ok, device=qkv.device).repeat_interleave(P)[:n]
-        out[b:b + 1] = torch_prefill_attention(qkv[b:b + 1], n_head, flat[0], flat[1], p, keep)
+        out[b:b + 1] = torch_prefill_attention(qkv[b:b + 1], n_head, flat[0], flat[1], p, keep,
+                                               *flat[2:])
     return out
 
 
@@ -934,12 +948,14 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                       v_cache: torch.Tensor, length: torch.Tensor,
                       pos: Union[None, int, Sequence[int]] = None,
                       block_table: Optional[torch.Tensor] = None, table_host=None,
-                      max_len: Optional[int] = None) -> torch.Tensor:
+                      max_len: Optional[int] = None, k_scale: Optional[torch.Tensor] = None,
+                      v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Chunked prefill (``csrc/attn_prefill.hip``): causal attention of a block of ``T`` new
     tokens over the cache, ``qkv [B, T, 3C]`` -> ``[B, T, C]``. The block's K / V must already be
     in the cache at ``[length, length + T)`` (:func:`kv_append`) and ``length`` not yet advanced;
     query ``i`` of row ``b`` attends cache positions ``0 .. length_b + i`` and every key and value
-    is read from the cache. bf16 caches only.
+    is read from the cache. ``k_scale`` / ``v_scale``: the row scales of an FP8 cache (module
+    docstring): the chunk then attends to its own rows in their quantised form too.
 
     It dispatches as :func:`kv_append` does: ``length.numel()`` 1 or ``B`` picks the shared or
     the per-sequence form (an empty slot, ``length[b] < 0``, gives zero rows), a ``block_table``
@@ -950,9 +966,7 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     other head dims the torch forms (:func:`torch_prefill_attention`)."""
     if qkv.dim() != 3 or qkv.shape[1] < 1:
         raise ValueError(f"prefill_attention takes qkv [B, T >= 1, 3C], got {tuple(qkv.shape)}")
-    if k_cache.dtype == E4M3 or v_cache.dtype == E4M3:
-        raise ValueError("prefill_attention reads a bf16 KV cache only (kv_cache_dtype='bf16'), "
-                         f"got {k_cache.dtype}")
+    fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     B, T, C3 = qkv.shape
     C = C3 // 3
     what = "prefill_attention"
@@ -969,14 +983,17 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
             raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
         if g is not None:
             g.check_mapped(host, [T] * B)
-    if use_hip(qkv) and (g.hip_ok(qkv, n_head, k_cache, v_cache, None, None) if g is not None
-                         else hip_supported(qkv, n_head, k_cache, v_cache)):
+    if use_hip(qkv) and (g.hip_ok(qkv, n_head, k_cache, v_cache, k_scale, v_scale)
+                         if g is not None
+                         else hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale)):
         D = C // n_head
         out = torch.empty(B, T, C, dtype=qkv.dtype, device=qkv.device)
-        name = "dlbb_attn_prefill" + ("_paged" if g is not None else "_seq" if seq else "")
+        name = ("dlbb_attn_prefill_fp8" if fp8 else "dlbb_attn_prefill") + \
+            ("_paged" if g is not None else "_seq" if seq else "")
+        scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
         table = g.args() if g is not None else ()
         check(getattr(_lib.lib(), name)(qkv.data_ptr(), C3, k_cache.data_ptr(),
-                                        v_cache.data_ptr(), length.data_ptr(), *table,
+                                        v_cache.data_ptr(), *scales, length.data_ptr(), *table,
                                         out.data_ptr(), C, B, T, n_head, D, L_max,
                                         1.0 / math.sqrt(D), _lib.stream(qkv.device)), name[5:])
         return out
@@ -985,10 +1002,11 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
         if max(host) + T > L_max:
             raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
     if g is not None:
-        return torch_prefill_attention_paged(qkv, n_head, k_cache, v_cache, g.host(), host, L_max)
+        return torch_prefill_attention_paged(qkv, n_head, k_cache, v_cache, g.host(), host, L_max,
+                                             k_scale, v_scale)
     if seq:
-        return torch_prefill_attention_seq(qkv, n_head, k_cache, v_cache, host)
-    return torch_prefill_attention(qkv, n_head, k_cache, v_cache, host[0])
+        return torch_prefill_attention_seq(qkv, n_head, k_cache, v_cache, host, k_scale, v_scale)
+    return torch_prefill_attention(qkv, n_head, k_cache, v_cache, host[0], None, k_scale, v_scale)
 
 
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,

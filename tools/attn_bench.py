@@ -6,7 +6,12 @@ of T queries over a cache that already holds ``prefix`` tokens, at the 7B head s
 and GPT-2's (H 12, D 64), B 1 / 8, T 512 / 2048, prefix 0 / 2048 / 8192. Per row, in one process
 and interleaved round by round: the kernel, torch SDPA under an explicit mask on the same cache, a
 copy of the K / V bytes the kernel reads and, at prefix 0, ``attn_fwd`` on the same qkv (the same
-FLOPs). One JSON line per row (default ``profiles/prefill_attention/attn_prefill.jsonl``)."""
+FLOPs). One JSON line per row (default ``profiles/prefill_attention/attn_prefill.jsonl``).
+
+``--prefill --fp8``: the FP8-cache form beside the bf16-cache kernel, and a copy of the bytes each
+reads (bf16 rows; codes + scales), over T 128 / 512 / 2048 and prefix 0 / 2048 / 8192 / 16384 (a
+short chunk over a long prefix is where the halved cache stream can show); no SDPA and no
+``attn_fwd`` candidates (default ``profiles/prefill_attention/attn_prefill_fp8.jsonl``)."""
 import argparse
 import json
 import os
@@ -35,7 +40,26 @@ def t_best(fn, iters=20, rounds=5):
     return best
 
 
-def prefill_rows(out_path):
+def _fp8_cache(kc, vc, qkv, H, prefix, length):
+    """The FP8 twin of a bf16 cache: the prefix rows re-appended quantised, T at a time (prefix
+    is a multiple of T), then the chunk as ``kv_append`` stores it."""
+    from distributed_llm_backend_benchmark_amd.ops import kv_append
+
+    B, T = qkv.shape[:2]
+    k8, v8 = (torch.zeros(c.shape, dtype=torch.float8_e4m3fn, device="cuda") for c in (kc, vc))
+    ks, vs = (torch.ones(kc.shape[:3], device="cuda") for _ in "kv")
+    buf = torch.zeros(B, T, 3, H, kc.shape[3], dtype=torch.bfloat16, device="cuda")
+    pos = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for s in range(0, prefix, T):
+        buf[:, :, 1] = kc[:, :, s:s + T].transpose(1, 2)
+        buf[:, :, 2] = vc[:, :, s:s + T].transpose(1, 2)
+        pos.fill_(s)
+        kv_append(buf.view(B, T, -1), H, k8, v8, pos, k_scale=ks, v_scale=vs)
+    kv_append(qkv, H, k8, v8, length, k_scale=ks, v_scale=vs)
+    return k8, v8, ks, vs
+
+
+def prefill_rows(out_path, fp8=False):
     import torch.nn.functional as F
 
     from distributed_llm_backend_benchmark_amd.ops import kv_append, prefill_attention
@@ -46,8 +70,8 @@ def prefill_rows(out_path):
     with open(out_path, "w") as fh:
         for H, D in ((32, 128), (12, 64)):
             for B in (1, 8):
-                for T in (512, 2048):
-                    for prefix in (0, 2048, 8192):
+                for T in (128, 512, 2048) if fp8 else (512, 2048):
+                    for prefix in (0, 2048, 8192, 16384) if fp8 else (0, 2048, 8192):
                         n = prefix + T
                         qkv = torch.randn(B, T, 3 * H * D, device="cuda", generator=gen).bfloat16()
                         kc = torch.randn(B, H, n, D, device="cuda", generator=gen).bfloat16()
@@ -62,8 +86,17 @@ def prefill_rows(out_path):
                                "kv_copy": lambda: (kc.clone(), vc.clone())}
                         if prefix == 0:
                             fns["attn_fwd"] = lambda: attn_fwd(qkv, H)
-                        err = float((fns["prefill"]().float() - fns["sdpa_masked"]().transpose(1, 2)
-                                     .reshape(B, T, H * D).float()).abs().max())
+                        if fp8:
+                            k8, v8, ks, vs = _fp8_cache(kc, vc, qkv, H, prefix, length)
+                            fns = {"prefill": fns["prefill"], "kv_copy": fns["kv_copy"],
+                                   "prefill_fp8": lambda: prefill_attention(
+                                       qkv, H, k8, v8, length, k_scale=ks, v_scale=vs),
+                                   "kv_copy_fp8": lambda: (k8.view(torch.uint8).clone(),
+                                                           v8.view(torch.uint8).clone(),
+                                                           ks.clone(), vs.clone())}
+                        other = (fns["prefill_fp8"]() if fp8 else fns["sdpa_masked"]()
+                                 .transpose(1, 2).reshape(B, T, H * D))
+                        err = float((fns["prefill"]().float() - other.float()).abs().max())
                         best = {k: 1e9 for k in fns}
                         for _ in range(5):                      # interleaved: one round of each
                             for k, fn in fns.items():
@@ -73,12 +106,17 @@ def prefill_rows(out_path):
                         rec = {"H": H, "D": D, "B": B, "T": T, "prefix": prefix,
                                "workgroups": -(-T // 128) * H * B,
                                "workgroups_per_cu": -(-T // 128) * H * B / 256,
-                               "max_abs_diff_vs_sdpa": err, "kv_bytes": nbytes,
+                               "max_abs_diff_vs_fp8" if fp8 else "max_abs_diff_vs_sdpa": err,
+                               "kv_bytes": nbytes,
                                "kv_copy_GBps": 2 * nbytes / best["kv_copy"] / 1e9,
-                               "tflops_prefill": fl / best["prefill"] / 1e12,
-                               "tflops_sdpa_masked": fl / best["sdpa_masked"] / 1e12}
+                               "tflops_prefill": fl / best["prefill"] / 1e12}
+                        if fp8:
+                            rec["kv_bytes_fp8"] = 2 * B * H * n * (D + 4)
+                            rec["tflops_prefill_fp8"] = fl / best["prefill_fp8"] / 1e12
+                        else:
+                            rec["tflops_sdpa_masked"] = fl / best["sdpa_masked"] / 1e12
                         rec.update({f"us_{k}": v * 1e6 for k, v in best.items()})
-                        if prefix == 0:
+                        if "attn_fwd" in best:
                             rec["tflops_attn_fwd"] = fl / best["attn_fwd"] / 1e12
                         print(json.dumps(rec), flush=True)
                         fh.write(json.dumps(rec) + "\n")
@@ -87,11 +125,14 @@ def prefill_rows(out_path):
 
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--prefill", action="store_true")
-_ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(
-    os.path.abspath(__file__))), "profiles", "prefill_attention", "attn_prefill.jsonl"))
+_ap.add_argument("--fp8", action="store_true", help="with --prefill: the FP8-cache rows")
+_ap.add_argument("--out", default=None)
 _args = _ap.parse_args()
 if _args.prefill:
-    prefill_rows(_args.out)
+    prefill_rows(_args.out or os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+        "prefill_attention", "attn_prefill_fp8.jsonl" if _args.fp8 else "attn_prefill.jsonl"),
+        _args.fp8)
     sys.exit(0)
 
 for B, T, H, D in ((16, 1024, 12, 64), (8, 2048, 12, 64), (4, 4096, 16, 64),
