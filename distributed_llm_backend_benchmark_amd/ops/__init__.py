@@ -13,7 +13,8 @@
 * :mod:`.xent` — fused softmax cross-entropy on bf16 logits; LM-head-fused linear + loss.
 * :mod:`.decode` — KV cache (bf16, or opt-in e4m3 codes with one fp32 scale per row), append, and
   single-query (decode) attention split over the keys; chunked prefill (``prefill_attention``):
-  causal attention of a block of new tokens over the cache.
+  causal attention of a block of new tokens over the cache; grouped-query decode (``n_kv_head=``):
+  one K / V read per KV head for the query heads sharing it, on MFMA.
 * :mod:`.embedding` — token + position embedding, backward accumulating in place (sinks).
 * :mod:`._lib` — loader; ``available()``, ``loaded_path()``.
 """
@@ -31,10 +32,10 @@ from .optim import FlatAdamW
 from .clip import GradClipper, grad_sumsq, clip_coef, sumsq_plan
 from .xent import cross_entropy, linear_cross_entropy
 from .attention import causal_attention
-from .decode import KVCache, kv_append, decode_attention, prefill_attention, CHUNK, CHUNK_FP8, PAGE_SIZE, PAGE_SIZES
+from .decode import KVCache, kv_append, decode_attention, prefill_attention, CHUNK, CHUNK_FP8, CHUNK_GQA, PAGE_SIZE, PAGE_SIZES
 from .embedding import embedding
 
-__all__ = ["KVCache", "kv_append", "decode_attention", "prefill_attention", "CHUNK", "CHUNK_FP8", "PAGE_SIZE", "PAGE_SIZES", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
+__all__ = ["KVCache", "kv_append", "decode_attention", "prefill_attention", "CHUNK", "CHUNK_FP8", "CHUNK_GQA", "PAGE_SIZE", "PAGE_SIZES", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
            "ChunkTable", "ScaleTable", "flatten_into", "linear", "layernorm", "bias_gelu",
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
            "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES",

@@ -221,6 +221,18 @@ _SIGS = {
                                             c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                             c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                                             c_float, c_void_p]),
+    # grouped-query decode (csrc/attn_decode_gqa.hip): H_q, H_kv where the forms above take H; the
+    # decode forms have no `fused` argument
+    "dlbb_kv_append_gqa": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                   c_int, c_int, c_int, c_int, c_void_p]),
+    "dlbb_kv_append_gqa_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dlbb_attn_decode_gqa": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_int, c_float, c_void_p]),
+    "dlbb_attn_decode_gqa_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_int, c_float, c_void_p]),
     "dlbb_rccl_unique_id_bytes": (c_int, []),
     "dlbb_rccl_get_unique_id": (c_int, [c_void_p]),
     "dlbb_rccl_init": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

@@ -108,6 +108,24 @@ FP8 cache (the ``dlbb_attn_prefill_fp8*`` entry points): the codes are widened e
 their way into LDS, ``k_scale[key]`` multiplies the fp32 score and ``v_scale[key]`` the fp32
 probability, and the chunk attends to its own rows in the quantised form the append stored, as a
 decode step does.
+
+Grouped-query heads (opt-in, ``n_kv_head=`` on :func:`kv_append` / :func:`decode_attention`,
+``KVCache(n_q_head=)``; ``csrc/attn_decode_gqa.hip``). The contract:
+
+* ``qkv`` is ``[B, T, (n_head + 2 n_kv_head) * D]``: the ``n_head`` query heads, then the
+  ``n_kv_head`` key heads, then the value heads. Query head ``h`` uses KV head ``h // G``,
+  ``G = n_head // n_kv_head``. The caches are ``[B, n_kv_head, L_max, D]`` bf16 contiguous.
+* ``n_kv_head=None`` or ``n_kv_head == n_head`` is the ungrouped path above, call for call.
+* :func:`decode_attention` keeps its contract (store at ``length``, attend ``length + 1`` keys,
+  ``length`` not advanced): an append launch, then a split in which one workgroup reads the K / V
+  rows of a chunk of :data:`CHUNK_GQA` keys ONCE for the ``G`` heads sharing them (MFMA), then the
+  combine. Shared and per-sequence lengths with every rule above; bit-identical from run to run,
+  and a ragged row has the bits of its batch-1 shared-length launch.
+* The HIP kernels serve head dim 64 / 128 and ``G`` in :data:`GQA_GROUPS` (another group size
+  raises ``ValueError`` there); the torch forms slice the three sections and expand K / V with
+  ``repeat_interleave`` for SDPA.
+* Not built: paged and FP8 grouped caches (``ValueError``), chunked prefill over a grouped cache,
+  more than one new token per step, a fused append, GQA in the models.
 """
 
 from __future__ import annotations
@@ -131,6 +149,14 @@ CHUNK = 256
 # 512 is 10-15 % faster on the rows of >= 128 MiB of bf16 K + V and 6-32 % slower on the smaller
 # head-dim-128 ones, 1024 is 3-17 % faster from 256 MiB and up to 67 % slower below
 CHUNK_FP8 = 256
+# keys per workgroup of the grouped-query split kernel (csrc/attn_decode_gqa.hip), a constant of
+# its own: a workgroup there serves the G query heads of one KV head, its four waves split the
+# chunk's keys and walk them in 32-key steps, so a chunk is a multiple of GQA_CHUNK_STEP keys. The
+# values measured are in docs/PERFORMANCE.md, "Grouped-query decode"
+CHUNK_GQA = 256
+GQA_CHUNK_STEP = 128
+# query heads per KV head that the grouped-query HIP kernels serve
+GQA_GROUPS = (2, 4, 8, 16)
 KV_DTYPES = ("bf16", "fp8")
 # page sizes of the paged cache (positions per page; csrc/attn_decode.hip checks the same set)
 PAGE_SIZES = (16, 32, 64, 128, 256)
@@ -233,17 +259,30 @@ class KVCache:
     :meth:`retire` and ``set_length(0)`` give pages back. A request the free list cannot satisfy
     raises ``ValueError`` and changes nothing; one that would change the table while the stream
     is capturing raises ``RuntimeError``, so a runner that replays one captured step calls
-    ``reserve_all(len_bound)`` before the capture."""
+    ``reserve_all(len_bound)`` before the capture.
+
+    ``n_q_head`` (default ``n_head_local``): grouped-query heads. ``n_head_local`` stays the heads
+    IN THE CACHE (the KV heads); ``n_q_head`` query heads share them, size the workspace and are
+    kept as ``n_q_head``. bf16 contiguous caches only."""
 
     def __init__(self, num_layers: int, batch: int, n_head_local: int, head_dim: int,
                  max_len: int, device, dtype=torch.bfloat16, kv_dtype: str = "bf16",
                  per_sequence: bool = False, page_size: Optional[int] = None,
-                 n_pages: Optional[int] = None):
+                 n_pages: Optional[int] = None, n_q_head: Optional[int] = None):
         if max_len < 1 or batch < 1:
             raise ValueError(f"KVCache needs batch >= 1 and max_len >= 1, got {batch}, {max_len}")
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"KVCache kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
         self.kv_dtype = kv_dtype
+        # grouped-query heads: the cache holds n_head_local KV heads, n_q_head query heads share
+        # them (module docstring, "Grouped-query heads"); None = one KV head per query head
+        self.n_q_head = int(n_head_local) if n_q_head is None else int(n_q_head)
+        gqa = self.n_q_head != int(n_head_local)
+        if gqa and (self.n_q_head < 1 or self.n_q_head % int(n_head_local)):
+            raise ValueError(f"KVCache n_q_head {n_q_head} is not a multiple of the "
+                             f"{n_head_local} KV heads")
+        if gqa and (kv_dtype != "bf16" or page_size is not None):
+            raise ValueError("KVCache: paged and FP8 grouped-query (GQA) caches are not built yet")
         self.per_sequence = bool(per_sequence) or page_size is not None
         self.page_size: Optional[int] = None
         self._pages: Optional[_PageAllocator] = None
@@ -292,8 +331,9 @@ class KVCache:
         # host upper bound of length + 1 for the split grid (None = max_len); a runner that
         # replays one captured step sets the final position here before the capture
         self.len_bound: Optional[int] = None
-        self.workspace = (torch.empty(workspace_numel(self.batch, self.n_head, self.head_dim,
-                                                      self.max_len, CHUNK_FP8 if fp8 else CHUNK),
+        self.workspace = (torch.empty(workspace_numel(self.batch, self.n_q_head, self.head_dim,
+                                                      self.max_len, CHUNK_GQA if gqa else
+                                                      CHUNK_FP8 if fp8 else CHUNK),
                                       dtype=torch.float32, device=self.device)
                           if self.num_layers else None)
 
@@ -453,6 +493,7 @@ class KVCache:
         s.kv_dtype, s.per_sequence = self.kv_dtype, False
         s.num_layers, s.batch = self.num_layers, 1
         s.n_head, s.head_dim, s.max_len = self.n_head, self.head_dim, self.max_len
+        s.n_q_head = self.n_q_head
         s.device = self.device
         s.page_size, s._pages, s.n_keep = self.page_size, self._pages, None
         s.extending = False
@@ -535,10 +576,37 @@ def _check_fp8_cache(k_cache, v_cache, k_scale, v_scale) -> bool:
     return True
 
 
+def _kv_heads(n_head: int, n_kv_head: Optional[int]) -> Optional[int]:
+    """``n_kv_head`` of a grouped-query call, None for today's layout (``None`` or ``n_head``);
+    ``ValueError`` unless the query heads are a whole multiple of the KV heads."""
+    if n_kv_head is None or int(n_kv_head) == int(n_head):
+        return None
+    n_kv_head = int(n_kv_head)
+    if n_kv_head < 1 or n_head % n_kv_head:
+        raise ValueError(f"n_head {n_head} is not a multiple of n_kv_head {n_kv_head}")
+    return n_kv_head
+
+
+def _views_gqa(qkv: torch.Tensor, n_head: int, n_kv_head: int):
+    """q ``[B, H_q, T, D]``, k / v ``[B, H_kv, T, D]`` views of the grouped layout ``[B, T,
+    (H_q + 2 H_kv) * D]``: the query heads, then the key heads, then the value heads."""
+    B, T, W = qkv.shape
+    heads = n_head + 2 * n_kv_head
+    if W % heads:
+        raise ValueError(f"qkv row of {W} is not (n_head + 2 n_kv_head) = {heads} heads")
+    x = qkv.view(B, T, heads, W // heads).transpose(1, 2)
+    return x[:, :n_head], x[:, n_head:n_head + n_kv_head], x[:, n_head + n_kv_head:]
+
+
 def torch_kv_append(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
-                    v_scale=None) -> None:
+                    v_scale=None, n_kv_head: Optional[int] = None) -> None:
     """Torch form of :func:`kv_append` at the host position ``pos``."""
     T = qkv.shape[1]
+    if n_kv_head is not None:                   # grouped layout: the bf16 cache only
+        _, k, v = _views_gqa(qkv, n_head, n_kv_head)
+        k_cache[:, :, pos:pos + T] = k
+        v_cache[:, :, pos:pos + T] = v
+        return
     _, k, v = _views(qkv, n_head)
     if k_scale is None:
         k_cache[:, :, pos:pos + T] = k
@@ -556,10 +624,19 @@ def dequantize(cache: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 
 def torch_decode_attention(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
-                           v_scale=None) -> torch.Tensor:
+                           v_scale=None, n_kv_head: Optional[int] = None) -> torch.Tensor:
     """Torch form of :func:`decode_attention` at the host position ``pos`` (not replayable
-    across positions: the slice bound is a host value)."""
+    across positions: the slice bound is a host value). ``n_kv_head``: the grouped layout; K / V
+    are expanded to the query heads with ``repeat_interleave`` for SDPA."""
     B, _, C3 = qkv.shape
+    if n_kv_head is not None:
+        torch_kv_append(qkv, n_head, k_cache, v_cache, pos, n_kv_head=n_kv_head)
+        q, _, _ = _views_gqa(qkv, n_head, n_kv_head)
+        G = n_head // n_kv_head
+        o = F.scaled_dot_product_attention(
+            q, k_cache[:, :, :pos + 1].repeat_interleave(G, dim=1),
+            v_cache[:, :, :pos + 1].repeat_interleave(G, dim=1))
+        return o.transpose(1, 2).reshape(B, 1, n_head * q.shape[3])
     torch_kv_append(qkv, n_head, k_cache, v_cache, pos, k_scale, v_scale)
     q, _, _ = _views(qkv, n_head)
     if k_scale is None:
@@ -591,7 +668,7 @@ def _host_positions(length: torch.Tensor, pos) -> List[int]:
 
 
 def torch_kv_append_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int], k_scale=None,
-                        v_scale=None) -> None:
+                        v_scale=None, n_kv_head: Optional[int] = None) -> None:
     """Torch form of the per-sequence :func:`kv_append`: row ``b`` is copied at the host position
     ``pos[b]``; nothing for an empty slot (``pos[b] < 0``)."""
     for b, p in enumerate(pos):
@@ -599,25 +676,27 @@ def torch_kv_append_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int], 
             continue
         torch_kv_append(qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p,
                         None if k_scale is None else k_scale[b:b + 1],
-                        None if v_scale is None else v_scale[b:b + 1])
+                        None if v_scale is None else v_scale[b:b + 1], n_kv_head)
 
 
 def torch_decode_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int],
-                               k_scale=None, v_scale=None) -> torch.Tensor:
+                               k_scale=None, v_scale=None,
+                               n_kv_head: Optional[int] = None) -> torch.Tensor:
     """Torch form of the per-sequence :func:`decode_attention` at the host positions ``pos``:
     row ``b`` is :func:`torch_decode_attention` on the batch-1 slice of its cache at ``pos[b]``,
     so a row has the bits of the shared-length form; empty slots give zero rows. (One SDPA over
     the batch with a boolean key mask was tried first: with a mask torch's CPU kernel rounds the
     scaled scores differently, and a bf16 row differed from the shared-length form by an ulp.)"""
     B, _, C3 = qkv.shape
-    out = torch.zeros(B, 1, C3 // 3, dtype=qkv.dtype, device=qkv.device)
+    C = C3 // 3 if n_kv_head is None else C3 // (n_head + 2 * n_kv_head) * n_head
+    out = torch.zeros(B, 1, C, dtype=qkv.dtype, device=qkv.device)
     for b, p in enumerate(pos):
         if p < 0:
             continue
         out[b:b + 1] = torch_decode_attention(
             qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p,
             None if k_scale is None else k_scale[b:b + 1],
-            None if v_scale is None else v_scale[b:b + 1])
+            None if v_scale is None else v_scale[b:b + 1], n_kv_head)
     return out
 
 
@@ -1009,12 +1088,123 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     return torch_prefill_attention(qkv, n_head, k_cache, v_cache, host[0], None, k_scale, v_scale)
 
 
+def _gqa_check(what: str, k_cache, v_cache, k_scale, v_scale, block_table) -> None:
+    """What a grouped-query call may not carry yet: a block table, an FP8 cache."""
+    if block_table is not None:
+        raise ValueError(f"{what}: paged grouped-query (GQA) caches are not built yet")
+    if k_scale is not None or v_scale is not None or E4M3 in (k_cache.dtype, v_cache.dtype):
+        raise ValueError(f"{what}: FP8 grouped-query (GQA) caches are not built yet")
+
+
+def _gqa_hip(what: str, qkv, n_head: int, n_kv_head: int, k_cache, v_cache) -> bool:
+    """True when the grouped-query HIP kernels take this call (a GPU tensor, head dim 64 / 128,
+    contiguous bf16 ``qkv`` and caches ``[B, H_kv, L_max, D]``); on that path a group size outside
+    :data:`GQA_GROUPS` raises ``ValueError``."""
+    heads = n_head + 2 * n_kv_head
+    if not use_hip(qkv) or qkv.dim() != 3 or qkv.dtype != torch.bfloat16 \
+            or not qkv.is_contiguous() or qkv.shape[2] % heads \
+            or qkv.shape[2] // heads not in HEAD_DIMS:
+        return False
+    shape = (qkv.shape[0], n_kv_head, k_cache.shape[2] if k_cache.dim() == 4 else -1,
+             qkv.shape[2] // heads)
+    if not all(t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == shape
+               for t in (k_cache, v_cache)):
+        return False
+    if n_head // n_kv_head not in GQA_GROUPS:
+        raise ValueError(f"{what}: {n_head} query heads over {n_kv_head} KV heads is a group of "
+                         f"{n_head // n_kv_head}; the HIP kernels serve {GQA_GROUPS}")
+    return True
+
+
+def _hip_append_gqa(qkv, n_head: int, n_kv_head: int, k_cache, v_cache, length, T: int) -> None:
+    B, _, W = qkv.shape
+    name = "dlbb_kv_append_gqa" + ("_seq" if length.numel() != 1 else "")
+    fn = getattr(_lib.lib(), name)
+    check(fn(qkv.data_ptr(), W, k_cache.data_ptr(), v_cache.data_ptr(), length.data_ptr(), B, T,
+             n_head, n_kv_head, W // (n_head + 2 * n_kv_head), k_cache.shape[2],
+             _lib.stream(qkv.device)), name[5:])
+
+
+def _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos) -> None:
+    """:func:`kv_append` on the grouped layout (module docstring, "Grouped-query heads")."""
+    T, L_max = qkv.shape[1], k_cache.shape[2]
+    seq = _per_sequence(length, qkv.shape[0], "kv_append")
+    host = None
+    if pos is not None:
+        host = _host_positions(length, pos) if seq else [int(pos)]
+        if max(host) + T > L_max:
+            raise ValueError(f"kv_append: position {max(host)} + {T} tokens > cache length "
+                             f"{L_max}")
+    if _gqa_hip("kv_append", qkv, n_head, n_kv_head, k_cache, v_cache):
+        _hip_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, T)
+        return
+    if host is None:
+        host = _host_positions(length, None) if seq else [_host_pos(length, None)]
+        if max(host) + T > L_max:
+            raise ValueError(f"kv_append: position {max(host)} + {T} tokens > cache length "
+                             f"{L_max}")
+    if seq:
+        torch_kv_append_seq(qkv, n_head, k_cache, v_cache, host, n_kv_head=n_kv_head)
+    else:
+        torch_kv_append(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head)
+
+
+def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_bound, workspace,
+                          pos, chunk, fused):
+    """:func:`decode_attention` on the grouped layout: the GQA append launch, then the split over
+    the KV heads and the combine (``csrc/attn_decode_gqa.hip``)."""
+    what = "decode_attention"
+    if fused:
+        raise ValueError(f"{what}: the grouped-query kernels have no fused append")
+    L_max = k_cache.shape[2]
+    B = qkv.shape[0]
+    seq = _per_sequence(length, B, what)
+    host = None
+    if pos is not None:
+        host = _host_positions(length, pos) if seq else [int(pos)]
+        if max(host) + 1 > L_max:
+            raise ValueError(f"{what}: position {max(host)} + 1 > cache length {L_max}")
+    if _gqa_hip(what, qkv, n_head, n_kv_head, k_cache, v_cache):
+        D = qkv.shape[2] // (n_head + 2 * n_kv_head)
+        C = n_head * D
+        chunk = int(chunk or CHUNK_GQA)
+        if chunk < 1 or chunk % GQA_CHUNK_STEP:
+            raise ValueError(f"{what}: a grouped-query chunk is a multiple of {GQA_CHUNK_STEP} "
+                             f"keys, got {chunk}")
+        bound = L_max if len_bound is None else max(1, min(int(len_bound), L_max))
+        if host is not None and max(host) + 1 > bound:
+            raise ValueError(f"{what}: position {max(host)} + 1 > len_bound {bound}")
+        need = workspace_numel(B, n_head, D, bound, chunk)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
+        elif workspace.numel() < need or workspace.dtype != torch.float32:
+            raise ValueError(f"{what}: workspace of {workspace.numel()} fp32 < {need}")
+        out = torch.empty(B, 1, C, dtype=qkv.dtype, device=qkv.device)
+        _hip_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, 1)
+        name = "dlbb_attn_decode_gqa" + ("_seq" if seq else "")
+        check(getattr(_lib.lib(), name)(qkv.data_ptr(), qkv.shape[2], k_cache.data_ptr(),
+                                        v_cache.data_ptr(), length.data_ptr(),
+                                        workspace.data_ptr(), out.data_ptr(), C, B, n_head,
+                                        n_kv_head, D, L_max, bound, chunk, 1.0 / math.sqrt(D),
+                                        _lib.stream(qkv.device)), name[5:])
+        return out
+    if host is None:
+        host = _host_positions(length, None) if seq else [_host_pos(length, None)]
+        if max(host) + 1 > L_max:
+            raise ValueError(f"{what}: position {max(host)} + 1 > cache length {L_max}")
+    if seq:
+        return torch_decode_attention_seq(qkv, n_head, k_cache, v_cache, host,
+                                          n_kv_head=n_kv_head)
+    return torch_decode_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head)
+
+
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
               length: torch.Tensor, pos: Union[None, int, Sequence[int]] = None,
               k_scale: Optional[torch.Tensor] = None,
               v_scale: Optional[torch.Tensor] = None,
               block_table: Optional[torch.Tensor] = None, table_host=None,
-              max_len: Optional[int] = None, n_keep: Optional[Sequence[int]] = None) -> None:
+              max_len: Optional[int] = None, n_keep: Optional[Sequence[int]] = None,
+              n_kv_head: Optional[int] = None) -> None:
     """K / V rows of ``qkv [B, T, 3C]`` -> cache positions ``[length, length + T)``. ``pos``:
     the host's copy of ``length`` (raises before launch on overflow; None on the HIP path = no
     host check, the kernel drops positions past the cache). ``k_scale`` / ``v_scale``: the row
@@ -1026,7 +1216,15 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
     are then the pools, ``max_len`` the logical cap (default ``max_pages * P``) and
     ``table_host`` the host mirror of the table that the ``pos`` check reads (default: the device
     table). ``n_keep``: per row, how many of the ``T`` tokens must land on mapped pages (default
-    ``T``; the padded prefill passes its ``prompt_lens``, the padding past them may be dropped)."""
+    ``T``; the padded prefill passes its ``prompt_lens``, the padding past them may be dropped).
+
+    ``n_kv_head`` (None or ``n_head`` = one KV head per query head, the paths above): the
+    grouped-query layout (module docstring): ``qkv`` is ``[B, T, (n_head + 2 n_kv_head) * D]`` and
+    the caches hold ``n_kv_head`` heads; bf16 contiguous caches only."""
+    n_kv_head = _kv_heads(n_head, n_kv_head)
+    if n_kv_head is not None:
+        _gqa_check("kv_append", k_cache, v_cache, k_scale, v_scale, block_table)
+        return _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos)
     if block_table is not None:
         return _kv_append_paged(qkv, n_head, k_cache, v_cache, length, pos, k_scale, v_scale,
                                 block_table, table_host, max_len, n_keep)
@@ -1065,7 +1263,8 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                      fused: Optional[bool] = None, k_scale: Optional[torch.Tensor] = None,
                      v_scale: Optional[torch.Tensor] = None,
                      block_table: Optional[torch.Tensor] = None, table_host=None,
-                     max_len: Optional[int] = None) -> torch.Tensor:
+                     max_len: Optional[int] = None,
+                     n_kv_head: Optional[int] = None) -> torch.Tensor:
     """One decode step of causal attention: ``qkv [B, 1, 3C]`` -> ``[B, 1, C]``; the token's
     K / V are stored at cache position ``length`` and the query attends over ``length + 1``
     keys. ``length`` is not advanced.
@@ -1085,9 +1284,20 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
 
     ``block_table`` (None = the contiguous caches): the paged form (module docstring); the caches
     are then the pools, ``max_len`` the logical cap (default ``max_pages * P``) and
-    ``table_host`` the host mirror of the table for the ``pos`` check."""
+    ``table_host`` the host mirror of the table for the ``pos`` check.
+
+    ``n_kv_head`` (None or ``n_head`` = the paths above): grouped-query heads (module docstring):
+    ``qkv`` is ``[B, 1, (n_head + 2 n_kv_head) * D]``, the caches hold ``n_kv_head`` heads and
+    query head ``h`` attends KV head ``h // (n_head // n_kv_head)``; the contract above holds.
+    The chunk default is :data:`CHUNK_GQA`; there is no fused append (an append launch, then the
+    split and the combine), and no paged or FP8 form yet (``ValueError``)."""
     if qkv.dim() != 3 or qkv.shape[1] != 1:
         raise ValueError(f"decode_attention takes qkv [B, 1, 3C], got {tuple(qkv.shape)}")
+    n_kv_head = _kv_heads(n_head, n_kv_head)
+    if n_kv_head is not None:
+        _gqa_check("decode_attention", k_cache, v_cache, k_scale, v_scale, block_table)
+        return _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_bound,
+                                     workspace, pos, chunk, fused)
     if block_table is not None:
         return _decode_attention_paged(qkv, n_head, k_cache, v_cache, length, len_bound,
                                        workspace, pos, chunk, fused, k_scale, v_scale,

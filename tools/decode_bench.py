@@ -41,6 +41,15 @@ per-sequence kernel at the same lengths) and ``copy_live``. With ``--fp8`` the s
 cache (``*_fp8``). ``paged_over_ragged`` is the ratio of the medians per ``P``, ``ragged_spread``
 the min and max round of ``ragged`` over its median, and ``within_ragged_spread`` whether the
 ratio lies inside it; ``paged_bits_equal_ragged`` checks the outputs' bytes.
+
+``--gqa`` times grouped-query decode instead (same protocol, same process; rows are
+``B,H_q,H_kv,D,L`` and go to ``profiles/gqa_decode/attn_decode_gqa.jsonl``): ``gqa`` is the decode
+step with ``n_kv_head=H_kv`` (append launch + split + combine, ``csrc/attn_decode_gqa.hip``),
+``expanded`` today's only alternative, the ungrouped step on the same K / V expanded to ``H_q``
+heads (``G`` times the bytes), ``copy`` a device copy of the K + V bytes the grouped kernel must
+read, ``gqa_chunk<N>`` the kernel at the other ``--gqa-chunks``. ``GBps`` is over the bytes each
+candidate reads; ``gqa_over_expanded`` stands beside ``one_over_G``, what the byte counts alone
+would give; ``us_min`` / ``us_max`` are the spread over the rounds.
 """
 
 from __future__ import annotations
@@ -424,9 +433,93 @@ def bench_paged_row(B, H, D, L, args):
     return row
 
 
+# grouped-query shapes a user runs (B, H_q, H_kv, D, L): 32 query heads over 8 / 4 KV heads
+GQA_ROWS = [(8, 32, kv, 128, L) for kv in (8, 4) for L in (2048, 8192, 32768)] + \
+    [(8, 32, 8, 64, 8192)]
+
+
+def bench_gqa_row(B, HQ, KV, D, L, args):
+    import torch
+
+    from distributed_llm_backend_benchmark_amd.ops import decode as dec
+
+    dev = torch.device("cuda", 0)
+    G = HQ // KV
+    kv_bytes = 2 * B * KV * L * D * 2                    # what the grouped kernel must read
+    nbuf = max(1, min(16, -(-args.rotate_mb * (1 << 20) // kv_bytes)))
+    g = torch.Generator(device=dev).manual_seed(L + HQ + KV)
+    caches = [torch.randn(2, B, KV, L, D, generator=g, device=dev).to(torch.bfloat16)
+              for _ in range(nbuf)]
+    # today's only alternative: the same K / V expanded to one KV head per query head
+    wide = [c.repeat_interleave(G, dim=2) for c in caches]
+    sink = torch.empty_like(caches[0])
+    tok = torch.randn(B, 1, HQ + 2 * KV, D, generator=g, device=dev).to(torch.bfloat16)
+    qkv = tok.reshape(B, 1, -1)
+    qkv_wide = torch.cat([tok[:, :, :HQ], tok[:, :, HQ:HQ + KV].repeat_interleave(G, dim=2),
+                          tok[:, :, HQ + KV:].repeat_interleave(G, dim=2)], 2).reshape(B, 1, -1)
+    length = torch.tensor([L - 1], dtype=torch.int32, device=dev)
+    chunks = sorted(set(args.gqa_chunks))
+    ws = torch.empty(dec.workspace_numel(B, HQ, D, L, min(chunks + [dec.CHUNK_GQA, dec.CHUNK])),
+                     dtype=torch.float32, device=dev)
+
+    def gqa(i, **kw):
+        kc, vc = caches[i % nbuf]
+        return dec.decode_attention(qkv, HQ, kc, vc, length, workspace=ws, n_kv_head=KV, **kw)
+
+    def expanded(i):
+        kc, vc = wide[i % nbuf]
+        return dec.decode_attention(qkv_wide, HQ, kc, vc, length, workspace=ws)
+
+    def copy(i):
+        sink.copy_(caches[i % nbuf])
+
+    cands = {"gqa": gqa, "expanded": expanded, "copy": copy}
+    for c in chunks:
+        if c != dec.CHUNK_GQA:
+            cands[f"gqa_chunk{c}"] = lambda i, c=c: gqa(i, chunk=c)
+    graphs = {}
+    for name, fn in cands.items():                       # warm every candidate, then capture
+        for i in range(nbuf + 1):
+            fn(i)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(args.inner):
+                fn(i)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    times = {n: [] for n in graphs}
+    for _ in range(args.rounds):                         # alternate the candidates
+        for name, gr in graphs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            gr.replay()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.inner)
+    ref = expanded(0).float()
+    us = {n: statistics.median(v) for n, v in times.items()}
+    return {"B": B, "H_q": HQ, "H_kv": KV, "G": G, "D": D, "L": L, "kv_bytes": kv_bytes,
+            "rotated_caches": nbuf, "chunk_gqa": dec.CHUNK_GQA, "chunk_expanded": dec.CHUNK,
+            "inner": args.inner, "rounds": args.rounds, "us": us,
+            "us_min": {n: min(v) for n, v in times.items()},
+            "us_max": {n: max(v) for n, v in times.items()},
+            "GBps": {n: (2 if n == "copy" else G if n == "expanded" else 1) * kv_bytes
+                     / (t * 1e-6) / 1e9 for n, t in us.items()},
+            "gqa_over_expanded": us["gqa"] / us["expanded"], "one_over_G": 1.0 / G,
+            "share_of_copy": kv_bytes / us["gqa"] / (2 * kv_bytes / us["copy"]),
+            "max_rel_diff_vs_expanded": float((gqa(0).float() - ref).abs().max()
+                                              / ref.abs().max())}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--gqa", action="store_true",
+                    help="time grouped-query decode instead: gqa, expanded, copy, gqa_chunk<N>; "
+                         "--rows are then B,H_q,H_kv,D,L")
+    ap.add_argument("--gqa-chunks", type=int, nargs="*", default=[256, 512, 1024])
     ap.add_argument("--rows", nargs="*", default=None, metavar="B,H,D,L")
     ap.add_argument("--chunks", type=int, nargs="*", default=[128, 256, 512])
     ap.add_argument("--fp8", action="store_true",
@@ -447,16 +540,28 @@ def main(argv=None) -> int:
                          "profiles/ragged_decode/attn_decode_ragged.jsonl)")
     args = ap.parse_args(argv)
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", *(("paged_decode", "attn_decode_paged.jsonl")
+        args.out = os.path.join(REPO, "profiles", *(("gqa_decode", "attn_decode_gqa.jsonl")
+                                                    if args.gqa else
+                                                    ("paged_decode", "attn_decode_paged.jsonl")
                                                     if args.paged else
                                                     ("ragged_decode", "attn_decode_ragged.jsonl")
                                                     if args.ragged
                                                     else ("decode", "attn_decode.jsonl")))
     rows = ([tuple(int(v) for v in r.split(",")) for r in args.rows] if args.rows
-            else DEFAULT_ROWS)
+            else GQA_ROWS if args.gqa else DEFAULT_ROWS)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
-        for B, H, D, L in rows:
+        for shape in rows if args.gqa else ():
+            row = bench_gqa_row(*shape, args)
+            f.write(json.dumps(row) + "\n")
+            f.flush()
+            print("B={} H_q={} H_kv={} D={} L={} ({:.0f} MiB K+V, {} caches): ".format(
+                      *shape, row["kv_bytes"] / 2**20, row["rotated_caches"]) +
+                  "  ".join(f"{n} {t:.1f} us [{row['us_min'][n]:.1f}, {row['us_max'][n]:.1f}] "
+                            f"({row['GBps'][n]:.0f} GB/s)" for n, t in row["us"].items()) +
+                  f"  gqa/expanded {row['gqa_over_expanded']:.3f} (1/G {row['one_over_G']:.3f})"
+                  f"  share_of_copy {row['share_of_copy']:.2f}", flush=True)
+        for B, H, D, L in () if args.gqa else rows:
             if args.paged:
                 row = bench_paged_row(B, H, D, L, args)
                 f.write(json.dumps(row) + "\n")
