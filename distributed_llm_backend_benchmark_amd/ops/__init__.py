@@ -13,8 +13,8 @@
 * :mod:`.xent` — fused softmax cross-entropy on bf16 logits; LM-head-fused linear + loss.
 * :mod:`.decode` — KV cache (bf16, or opt-in e4m3 codes with one fp32 scale per row), append, and
   single-query (decode) attention split over the keys; chunked prefill (``prefill_attention``):
-  causal attention of a block of new tokens over the cache; grouped-query decode (``n_kv_head=``):
-  one K / V read per KV head for the query heads sharing it, on MFMA.
+  causal attention of a block of new tokens over the cache; grouped-query decode and chunked
+  prefill (``n_kv_head=``): one K / V read per KV head for the query heads sharing it, on MFMA.
 * :mod:`.embedding` — token + position embedding, backward accumulating in place (sinks).
 * :mod:`._lib` — loader; ``available()``, ``loaded_path()``.
 """

@@ -233,6 +233,14 @@ _SIGS = {
     "dlbb_attn_decode_gqa_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                          c_int, c_int, c_int, c_float, c_void_p]),
+    # grouped-query chunked prefill (csrc/attn_prefill_gqa.hip): dlbb_attn_prefill's arguments
+    # with H_q, H_kv where it takes H
+    "dlbb_attn_prefill_gqa": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                      c_void_p]),
+    "dlbb_attn_prefill_gqa_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_float, c_void_p]),
     "dlbb_rccl_unique_id_bytes": (c_int, []),
     "dlbb_rccl_get_unique_id": (c_int, [c_void_p]),
     "dlbb_rccl_init": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

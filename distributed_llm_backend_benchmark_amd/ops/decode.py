@@ -109,8 +109,9 @@ their way into LDS, ``k_scale[key]`` multiplies the fp32 score and ``v_scale[key
 probability, and the chunk attends to its own rows in the quantised form the append stored, as a
 decode step does.
 
-Grouped-query heads (opt-in, ``n_kv_head=`` on :func:`kv_append` / :func:`decode_attention`,
-``KVCache(n_q_head=)``; ``csrc/attn_decode_gqa.hip``). The contract:
+Grouped-query heads (opt-in, ``n_kv_head=`` on :func:`kv_append` / :func:`decode_attention` /
+:func:`prefill_attention`, ``KVCache(n_q_head=)``; ``csrc/attn_decode_gqa.hip``,
+``csrc/attn_prefill_gqa.hip``). The contract:
 
 * ``qkv`` is ``[B, T, (n_head + 2 n_kv_head) * D]``: the ``n_head`` query heads, then the
   ``n_kv_head`` key heads, then the value heads. Query head ``h`` uses KV head ``h // G``,
@@ -124,8 +125,16 @@ Grouped-query heads (opt-in, ``n_kv_head=`` on :func:`kv_append` / :func:`decode
 * The HIP kernels serve head dim 64 / 128 and ``G`` in :data:`GQA_GROUPS` (another group size
   raises ``ValueError`` there); the torch forms slice the three sections and expand K / V with
   ``repeat_interleave`` for SDPA.
-* Not built: paged and FP8 grouped caches (``ValueError``), chunked prefill over a grouped cache,
-  more than one new token per step, a fused append, GQA in the models.
+* :func:`prefill_attention` keeps its contract too (the block appended by :func:`kv_append` with
+  the same ``n_kv_head``, ``length`` not advanced, bottom-right causal mask, every key and value
+  from the cache) and returns ``[B, T, n_head * D]``. One launch: the 128 rows of a workgroup are
+  the (token, query head) pairs of ``128 / G`` tokens and ONE KV head, so a K / V tile staged into
+  LDS serves the ``G`` heads sharing it and the cache is read once per KV head. A block of a few
+  tokens (``T * G <= 128``) is one workgroup per KV head and batch row: the multi-token step of a
+  grouped decode, with no split over the keys. Shared and per-sequence lengths, bit-identical from
+  run to run, a ragged row has the bits of its batch-1 shared-length launch.
+* Not built: paged and FP8 grouped caches (``ValueError``), a key split for short blocks over a
+  long prefix, a fused append, GQA in the models.
 """
 
 from __future__ import annotations
@@ -955,17 +964,25 @@ def _decode_attention_paged(qkv, n_head, k_pool, v_pool, length, len_bound, work
 
 def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
                             keep: Optional[torch.Tensor] = None, k_scale=None,
-                            v_scale=None) -> torch.Tensor:
+                            v_scale=None, n_kv_head: Optional[int] = None) -> torch.Tensor:
     """Torch form of :func:`prefill_attention` at the host position ``pos``: fp32 SDPA of the
     ``T`` queries over ``cache[:, :, :pos + T]`` (the chunk already appended; an FP8 cache is
     dequantised with :func:`dequantize`) under an explicit bottom-right causal mask: query ``i``
     sees positions ``0 .. pos + i``. ``keep``: a boolean ``[pos + T]`` key mask on top (the paged
     form's unmapped pages); a key it removes has its K / V rows replaced by zeros, so nothing
-    stale reaches the product."""
+    stale reaches the product. ``n_kv_head``: the grouped layout (the bf16 cache only); the live
+    cache rows are expanded to the query heads with ``repeat_interleave`` in fp32."""
     B, T, C3 = qkv.shape
     n = min(pos + T, k_cache.shape[2])
-    q, _, _ = _views(qkv, n_head)
     mask = torch.ones(T, n, dtype=torch.bool, device=qkv.device).tril(diagonal=pos)
+    if n_kv_head is not None:
+        q, _, _ = _views_gqa(qkv, n_head, n_kv_head)
+        G = n_head // n_kv_head
+        o = F.scaled_dot_product_attention(
+            q.float(), k_cache[:, :, :n].float().repeat_interleave(G, 1),
+            v_cache[:, :, :n].float().repeat_interleave(G, 1), attn_mask=mask)
+        return o.to(qkv.dtype).transpose(1, 2).reshape(B, T, n_head * q.shape[3])
+    q, _, _ = _views(qkv, n_head)
     if k_scale is None:
         k, v = k_cache[:, :, :n].float(), v_cache[:, :, :n].float()
     else:
@@ -980,18 +997,20 @@ def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
 
 
 def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int],
-                                k_scale=None, v_scale=None) -> torch.Tensor:
+                                k_scale=None, v_scale=None,
+                                n_kv_head: Optional[int] = None) -> torch.Tensor:
     """Torch form of the per-sequence :func:`prefill_attention`: row ``b`` is
     :func:`torch_prefill_attention` on its batch-1 slice at ``pos[b]``; empty slots give zero
     rows."""
     B, T, C3 = qkv.shape
-    out = torch.zeros(B, T, C3 // 3, dtype=qkv.dtype, device=qkv.device)
+    C = C3 // 3 if n_kv_head is None else C3 // (n_head + 2 * n_kv_head) * n_head
+    out = torch.zeros(B, T, C, dtype=qkv.dtype, device=qkv.device)
     for b, p in enumerate(pos):
         if p >= 0:
             out[b:b + 1] = torch_prefill_attention(
                 qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p, None,
                 None if k_scale is None else k_scale[b:b + 1],
-                None if v_scale is None else v_scale[b:b + 1])
+                None if v_scale is None else v_scale[b:b + 1], n_kv_head)
     return out
 
 
@@ -1028,7 +1047,8 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                       pos: Union[None, int, Sequence[int]] = None,
                       block_table: Optional[torch.Tensor] = None, table_host=None,
                       max_len: Optional[int] = None, k_scale: Optional[torch.Tensor] = None,
-                      v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      v_scale: Optional[torch.Tensor] = None,
+                      n_kv_head: Optional[int] = None) -> torch.Tensor:
     """Chunked prefill (``csrc/attn_prefill.hip``): causal attention of a block of ``T`` new
     tokens over the cache, ``qkv [B, T, 3C]`` -> ``[B, T, C]``. The block's K / V must already be
     in the cache at ``[length, length + T)`` (:func:`kv_append`) and ``length`` not yet advanced;
@@ -1042,9 +1062,19 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     ``pos``: the host's copy of ``length`` for the overflow check and, paged, for the check that
     every page of ``[0, pos_b + T)`` is mapped (None on the HIP path = no host check). GPU
     tensors with head dim 64 / 128 take the HIP kernel; CPU tensors, ``DLBB_KERNELS=torch`` and
-    other head dims the torch forms (:func:`torch_prefill_attention`)."""
+    other head dims the torch forms (:func:`torch_prefill_attention`).
+
+    ``n_kv_head`` (None or ``n_head`` = the paths above): grouped-query heads (module docstring,
+    ``csrc/attn_prefill_gqa.hip``): ``qkv`` is ``[B, T, (n_head + 2 n_kv_head) * D]``, the caches
+    hold ``n_kv_head`` heads (:func:`kv_append` with the same ``n_kv_head`` wrote the block),
+    query head ``h`` attends KV head ``h // (n_head // n_kv_head)`` and the result is ``[B, T,
+    n_head * D]``. Shared and per-sequence lengths; no paged or FP8 form yet (``ValueError``)."""
     if qkv.dim() != 3 or qkv.shape[1] < 1:
         raise ValueError(f"prefill_attention takes qkv [B, T >= 1, 3C], got {tuple(qkv.shape)}")
+    n_kv_head = _kv_heads(n_head, n_kv_head)
+    if n_kv_head is not None:
+        _gqa_check("prefill_attention", k_cache, v_cache, k_scale, v_scale, block_table)
+        return _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos)
     fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     B, T, C3 = qkv.shape
     C = C3 // 3
@@ -1196,6 +1226,39 @@ def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_
         return torch_decode_attention_seq(qkv, n_head, k_cache, v_cache, host,
                                           n_kv_head=n_kv_head)
     return torch_decode_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head)
+
+
+def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos):
+    """:func:`prefill_attention` on the grouped layout: one launch of
+    ``csrc/attn_prefill_gqa.hip``, whose workgroups take the (token, query head) rows of one KV
+    head, so a K / V tile is staged once for the ``G`` heads sharing it."""
+    what = "prefill_attention"
+    B, T, W = qkv.shape
+    L_max = k_cache.shape[2]
+    seq = _per_sequence(length, B, what)
+    host = None
+    if pos is not None:
+        host = _host_positions(length, pos) if seq else [int(pos)]
+        if max(host) + T > L_max:
+            raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
+    if _gqa_hip(what, qkv, n_head, n_kv_head, k_cache, v_cache):
+        D = W // (n_head + 2 * n_kv_head)
+        C = n_head * D
+        out = torch.empty(B, T, C, dtype=qkv.dtype, device=qkv.device)
+        name = "dlbb_attn_prefill_gqa" + ("_seq" if seq else "")
+        check(getattr(_lib.lib(), name)(qkv.data_ptr(), W, k_cache.data_ptr(), v_cache.data_ptr(),
+                                        length.data_ptr(), out.data_ptr(), C, B, T, n_head,
+                                        n_kv_head, D, L_max, 1.0 / math.sqrt(D),
+                                        _lib.stream(qkv.device)), name[5:])
+        return out
+    if host is None:
+        host = _host_positions(length, None) if seq else [_host_pos(length, None)]
+        if max(host) + T > L_max:
+            raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
+    if seq:
+        return torch_prefill_attention_seq(qkv, n_head, k_cache, v_cache, host,
+                                           n_kv_head=n_kv_head)
+    return torch_prefill_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head)
 
 
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,

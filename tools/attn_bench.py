@@ -11,7 +11,12 @@ FLOPs). One JSON line per row (default ``profiles/prefill_attention/attn_prefill
 ``--prefill --fp8``: the FP8-cache form beside the bf16-cache kernel, and a copy of the bytes each
 reads (bf16 rows; codes + scales), over T 128 / 512 / 2048 and prefix 0 / 2048 / 8192 / 16384 (a
 short chunk over a long prefix is where the halved cache stream can show); no SDPA and no
-``attn_fwd`` candidates (default ``profiles/prefill_attention/attn_prefill_fp8.jsonl``)."""
+``attn_fwd`` candidates (default ``profiles/prefill_attention/attn_prefill_fp8.jsonl``).
+
+``--prefill --gqa``: the grouped-query kernel (``n_kv_head=``) at H_q 32, D 128, H_kv 8 / 4, T 8 /
+128 / 512, prefix 0 / 2048 / 8192, B 1 / 8, beside the ungrouped kernel on the cache repeated to
+32 heads and a copy of the grouped K + V bytes; median [min, max] over interleaved rounds (default
+``profiles/prefill_gqa/attn_prefill_gqa.jsonl``)."""
 import argparse
 import json
 import os
@@ -123,11 +128,77 @@ def prefill_rows(out_path, fp8=False):
                         fh.flush()
 
 
+def prefill_gqa_rows(out_path, rounds=7):
+    """Grouped-query chunked prefill at H_q 32, D 128: ``gqa`` (the grouped cache), ``expanded``
+    (the ungrouped kernel on the cache repeated to 32 heads, built outside the timed region) and
+    ``kv_copy`` (a device copy of the grouped K + V bytes read), one timed window of each per
+    round, round by round; per candidate the median, min and max over the rounds."""
+    import statistics
+
+    from distributed_llm_backend_benchmark_amd.ops import kv_append, prefill_attention
+
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    HQ, D = 32, 128
+    with open(out_path, "w") as fh:
+        for HKV in (8, 4):
+            G = HQ // HKV
+            for B in (1, 8):
+                for T in (8, 128, 512):
+                    for prefix in (0, 2048, 8192):
+                        n = prefix + T
+                        qkv = torch.randn(B, T, (HQ + 2 * HKV) * D, device="cuda",
+                                          generator=gen).bfloat16()
+                        kc = torch.randn(B, HKV, n, D, device="cuda", generator=gen).bfloat16()
+                        vc = torch.randn(B, HKV, n, D, device="cuda", generator=gen).bfloat16()
+                        length = torch.tensor([prefix], dtype=torch.int32, device="cuda")
+                        kv_append(qkv, HQ, kc, vc, length, n_kv_head=HKV)
+                        x = qkv.view(B, T, HQ + 2 * HKV, D)
+                        mha = torch.stack(
+                            [x[:, :, :HQ], x[:, :, HQ:HQ + HKV].repeat_interleave(G, 2),
+                             x[:, :, HQ + HKV:].repeat_interleave(G, 2)], 2).reshape(B, T, -1)
+                        ke, ve = kc.repeat_interleave(G, 1), vc.repeat_interleave(G, 1)
+                        fns = {"gqa": lambda: prefill_attention(qkv, HQ, kc, vc, length,
+                                                                n_kv_head=HKV),
+                               "expanded": lambda: prefill_attention(mha, HQ, ke, ve, length),
+                               "kv_copy": lambda: (kc.clone(), vc.clone())}
+                        err = float((fns["gqa"]().float() - fns["expanded"]().float())
+                                    .abs().max())
+                        # a timed window of >= 20 ms per candidate and round
+                        iters = {k: max(10, min(2000, int(0.02 / t_best(fn, iters=5, rounds=1))))
+                                 for k, fn in fns.items()}
+                        times = {k: [] for k in fns}
+                        for _ in range(rounds):                 # interleaved: one round of each
+                            for k, fn in fns.items():
+                                times[k].append(t_best(fn, iters=iters[k], rounds=1) * 1e6)
+                        med = {k: statistics.median(v) for k, v in times.items()}
+                        rec = {"H_q": HQ, "H_kv": HKV, "D": D, "B": B, "T": T, "prefix": prefix,
+                               "workgroups_gqa": -(-T * G // 128) * HKV * B,
+                               "workgroups_expanded": -(-T // 128) * HQ * B,
+                               "max_abs_diff_gqa_vs_expanded": err,
+                               "kv_bytes_gqa": 2 * B * HKV * n * D * 2,
+                               "kv_bytes_expanded": 2 * B * HQ * n * D * 2,
+                               "gqa_over_expanded": med["gqa"] / med["expanded"]}
+                        for k, v in times.items():
+                            rec.update({f"us_{k}": med[k], f"us_{k}_min": min(v),
+                                        f"us_{k}_max": max(v)})
+                        print(json.dumps(rec), flush=True)
+                        fh.write(json.dumps(rec) + "\n")
+                        fh.flush()
+
+
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--prefill", action="store_true")
 _ap.add_argument("--fp8", action="store_true", help="with --prefill: the FP8-cache rows")
+_ap.add_argument("--gqa", action="store_true",
+                 help="with --prefill: the grouped-query kernel beside the expanded cache")
 _ap.add_argument("--out", default=None)
 _args = _ap.parse_args()
+if _args.prefill and _args.gqa:
+    prefill_gqa_rows(_args.out or os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "prefill_gqa",
+        "attn_prefill_gqa.jsonl"))
+    sys.exit(0)
 if _args.prefill:
     prefill_rows(_args.out or os.path.join(
         os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
