@@ -33,9 +33,10 @@ from .clip import GradClipper, grad_sumsq, clip_coef, sumsq_plan
 from .xent import cross_entropy, linear_cross_entropy
 from .attention import causal_attention
 from .decode import KVCache, kv_append, decode_attention, prefill_attention, CHUNK, CHUNK_FP8, CHUNK_GQA, PAGE_SIZE, PAGE_SIZES
+from .decode import CHUNK_PREFILL_GQA, GQA_CHUNK_STEP, prefill_workspace_numel
 from .embedding import embedding
 
-__all__ = ["KVCache", "kv_append", "decode_attention", "prefill_attention", "CHUNK", "CHUNK_FP8", "CHUNK_GQA", "PAGE_SIZE", "PAGE_SIZES", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
+__all__ = ["KVCache", "kv_append", "decode_attention", "prefill_attention", "CHUNK", "CHUNK_FP8", "CHUNK_GQA", "PAGE_SIZE", "PAGE_SIZES", "CHUNK_PREFILL_GQA", "GQA_CHUNK_STEP", "prefill_workspace_numel", "causal_attention", "available", "loaded_path", "KernelError", "reduce_sum", "cast", "pack_rows",
            "ChunkTable", "ScaleTable", "flatten_into", "linear", "layernorm", "bias_gelu",
            "FlatAdamW", "cross_entropy", "linear_cross_entropy", "embedding", "quantize_rows",
            "linear_fp8", "fp8_linear", "linear_w8", "w8_linear", "W8_LAUNCHES",

@@ -241,6 +241,16 @@ _SIGS = {
     "dlbb_attn_prefill_gqa_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_float, c_void_p]),
+    # the same with the keys split over workgroups (csrc/attn_prefill_gqa_split.hip): ws before
+    # out, len_bound and chunk after L_max
+    "dlbb_attn_prefill_gqa_split": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                            c_int, c_int, c_int, c_int, c_int, c_float,
+                                            c_void_p]),
+    "dlbb_attn_prefill_gqa_split_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                                c_int, c_int, c_int, c_int, c_int, c_float,
+                                                c_void_p]),
     "dlbb_rccl_unique_id_bytes": (c_int, []),
     "dlbb_rccl_get_unique_id": (c_int, [c_void_p]),
     "dlbb_rccl_init": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

@@ -42,8 +42,11 @@ _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # compared bit for bit between its three forms. attn_decode_gqa.hip: the same softmax and rescale
 # loops, and its ragged rows are compared bit for bit with batch-1 shared-length launches.
 # attn_prefill_gqa.hip: attn_prefill.hip's loops on another row mapping, compared the same way.
+# attn_prefill_gqa_split.hip: attn_prefill_gqa.hip's tile body per key chunk, and a merge whose
+# rows are compared bit for bit between the per-sequence and the shared-length launch.
 EXTRA_CFLAGS = {"gemm_mxfp4.hip": _NO_PK_F32, "attn_prefill.hip": _NO_PK_F32,
-                "attn_decode_gqa.hip": _NO_PK_F32, "attn_prefill_gqa.hip": _NO_PK_F32}
+                "attn_decode_gqa.hip": _NO_PK_F32, "attn_prefill_gqa.hip": _NO_PK_F32,
+                "attn_prefill_gqa_split.hip": _NO_PK_F32}
 
 
 def hipcc() -> str:

@@ -133,8 +133,19 @@ Grouped-query heads (opt-in, ``n_kv_head=`` on :func:`kv_append` / :func:`decode
   tokens (``T * G <= 128``) is one workgroup per KV head and batch row: the multi-token step of a
   grouped decode, with no split over the keys. Shared and per-sequence lengths, bit-identical from
   run to run, a ragged row has the bits of its batch-1 shared-length launch.
-* Not built: paged and FP8 grouped caches (``ValueError``), a key split for short blocks over a
-  long prefix, a fused append, GQA in the models.
+* ``prefill_attention(..., key_split=C)`` (opt-in; ``csrc/attn_prefill_gqa_split.hip``) is the
+  form for such a short block over a LONG prefix: the keys are cut into chunks of ``C`` keys
+  (:data:`CHUNK_PREFILL_GQA`; a multiple of :data:`GQA_CHUNK_STEP`), a workgroup is (chunk, token
+  block, KV head, batch row) and writes unnormalised fp32 partials ``m, l, o[D]`` into a workspace
+  ``[B, n_head, T, n_chunks, D + 2]`` (:func:`prefill_workspace_numel`), and a combine kernel
+  merges a row's live chunks in chunk order. ``len_bound`` (host upper bound of ``length + T``)
+  sizes the grid, chunks past the device length exit at once, and the workspace needs no
+  clearing. The contract and the error bound are the one-launch kernel's, the bits are not (the
+  merge is another fp32 order); bit-identical from run to run, a ragged row has the bits of its
+  batch-1 shared-length launch at the same ``key_split`` and ``len_bound``. Nothing picks it by
+  itself; the torch forms ignore ``key_split``.
+* Not built: paged and FP8 grouped caches (``ValueError``), an automatic choice between the split
+  and the one-launch prefill, a fused append, GQA in the models.
 """
 
 from __future__ import annotations
@@ -164,6 +175,13 @@ CHUNK_FP8 = 256
 # values measured are in docs/PERFORMANCE.md, "Grouped-query decode"
 CHUNK_GQA = 256
 GQA_CHUNK_STEP = 128
+# keys per workgroup of the key-split grouped-query prefill (csrc/attn_prefill_gqa_split.hip), the
+# value to pass as prefill_attention(key_split=): nothing picks the split form by itself. A
+# multiple of GQA_CHUNK_STEP too (whole tiles at both head dims). 128 / 256 / 512 / 1024 measured
+# on the B 1 rows (docs/PERFORMANCE.md, "Key-split grouped-query prefill"): 512 is the one chunk
+# within 1.3x of the best chunk on every row with a prefix (256 is best for 8 tokens over 2048
+# keys and up to 2x off at T 512, 1024 the reverse)
+CHUNK_PREFILL_GQA = 512
 # query heads per KV head that the grouped-query HIP kernels serve
 GQA_GROUPS = (2, 4, 8, 16)
 KV_DTYPES = ("bf16", "fp8")
@@ -185,6 +203,13 @@ def workspace_numel(batch: int, n_head: int, head_dim: int, max_len: int,
                     chunk: int = CHUNK) -> int:
     """fp32 elements of the split kernel's partials: ``[B, H, n_chunks, D + 2]``."""
     return batch * n_head * ((max_len + chunk - 1) // chunk) * (head_dim + 2)
+
+
+def prefill_workspace_numel(batch: int, n_head: int, head_dim: int, T: int, max_len: int,
+                            chunk: int = CHUNK_PREFILL_GQA) -> int:
+    """fp32 elements of the key-split grouped prefill's partials: ``[B, H_q, T, n_chunks,
+    D + 2]`` (``prefill_attention(key_split=chunk)``; ``max_len``: its ``len_bound``)."""
+    return batch * n_head * T * ((max_len + chunk - 1) // chunk) * (head_dim + 2)
 
 
 def check_page_size(page_size: int, chunk: Optional[int] = None) -> int:
@@ -1048,7 +1073,9 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                       block_table: Optional[torch.Tensor] = None, table_host=None,
                       max_len: Optional[int] = None, k_scale: Optional[torch.Tensor] = None,
                       v_scale: Optional[torch.Tensor] = None,
-                      n_kv_head: Optional[int] = None) -> torch.Tensor:
+                      n_kv_head: Optional[int] = None, key_split: Optional[int] = None,
+                      len_bound: Optional[int] = None,
+                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Chunked prefill (``csrc/attn_prefill.hip``): causal attention of a block of ``T`` new
     tokens over the cache, ``qkv [B, T, 3C]`` -> ``[B, T, C]``. The block's K / V must already be
     in the cache at ``[length, length + T)`` (:func:`kv_append`) and ``length`` not yet advanced;
@@ -1068,13 +1095,35 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     ``csrc/attn_prefill_gqa.hip``): ``qkv`` is ``[B, T, (n_head + 2 n_kv_head) * D]``, the caches
     hold ``n_kv_head`` heads (:func:`kv_append` with the same ``n_kv_head`` wrote the block),
     query head ``h`` attends KV head ``h // (n_head // n_kv_head)`` and the result is ``[B, T,
-    n_head * D]``. Shared and per-sequence lengths; no paged or FP8 form yet (``ValueError``)."""
+    n_head * D]``. Shared and per-sequence lengths; no paged or FP8 form yet (``ValueError``).
+
+    ``key_split`` (grouped heads only; None = the one-launch kernel above, call for call): the keys
+    of a row are cut into chunks of ``key_split`` keys (a multiple of :data:`GQA_CHUNK_STEP`; pass
+    :data:`CHUNK_PREFILL_GQA`) that run in different workgroups, and a second kernel merges the
+    chunks (``csrc/attn_prefill_gqa_split.hip``): for a block of a few tokens over a long prefix,
+    which otherwise is ``n_kv_head * B`` workgroups walking the whole prefix. ``len_bound``: host
+    upper bound of ``length + T`` that sizes the grid (default: the cache length; chunks past the
+    device length exit at once, so one captured launch pair serves every position below it).
+    ``workspace``: fp32 partials of :func:`prefill_workspace_numel` elements at ``len_bound``
+    (allocated per call when None; it needs no clearing). Same contract and bound as the unsplit
+    kernel, not its bits; bit-identical from run to run. Nothing chooses the split by itself, and
+    the torch forms ignore it."""
     if qkv.dim() != 3 or qkv.shape[1] < 1:
         raise ValueError(f"prefill_attention takes qkv [B, T >= 1, 3C], got {tuple(qkv.shape)}")
     n_kv_head = _kv_heads(n_head, n_kv_head)
+    if key_split is None and (len_bound is not None or workspace is not None):
+        raise ValueError("prefill_attention: len_bound and workspace go with key_split")
+    if key_split is not None:
+        if int(key_split) < 1 or int(key_split) % GQA_CHUNK_STEP:
+            raise ValueError(f"prefill_attention: key_split is a positive multiple of "
+                             f"{GQA_CHUNK_STEP} keys, got {key_split}")
+        if n_kv_head is None:
+            raise ValueError("prefill_attention: the ungrouped kernels have no key split "
+                             "(key_split goes with n_kv_head < n_head)")
     if n_kv_head is not None:
         _gqa_check("prefill_attention", k_cache, v_cache, k_scale, v_scale, block_table)
-        return _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos)
+        return _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos,
+                                      key_split, len_bound, workspace)
     fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     B, T, C3 = qkv.shape
     C = C3 // 3
@@ -1228,10 +1277,13 @@ def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_
     return torch_decode_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head)
 
 
-def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos):
+def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos,
+                           key_split=None, len_bound=None, workspace=None):
     """:func:`prefill_attention` on the grouped layout: one launch of
     ``csrc/attn_prefill_gqa.hip``, whose workgroups take the (token, query head) rows of one KV
-    head, so a K / V tile is staged once for the ``G`` heads sharing it."""
+    head, so a K / V tile is staged once for the ``G`` heads sharing it. With ``key_split`` (a
+    chunk in keys, checked by the caller) the split and combine launches of
+    ``csrc/attn_prefill_gqa_split.hip`` instead."""
     what = "prefill_attention"
     B, T, W = qkv.shape
     L_max = k_cache.shape[2]
@@ -1241,10 +1293,31 @@ def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos
         host = _host_positions(length, pos) if seq else [int(pos)]
         if max(host) + T > L_max:
             raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
+    D = W // (n_head + 2 * n_kv_head)
+    if key_split is not None:
+        chunk = int(key_split)
+        bound = L_max if len_bound is None else max(1, min(int(len_bound), L_max))
+        if host is not None and max(host) + T > bound:
+            raise ValueError(f"{what}: position {max(host)} + {T} tokens > len_bound {bound}")
+        need = prefill_workspace_numel(B, n_head, D, T, bound, chunk)
+        if workspace is not None and (workspace.dtype != torch.float32
+                                      or workspace.numel() < need):
+            raise ValueError(f"{what}: workspace of {workspace.numel()} {workspace.dtype} "
+                             f"elements, need {need} fp32")
     if _gqa_hip(what, qkv, n_head, n_kv_head, k_cache, v_cache):
-        D = W // (n_head + 2 * n_kv_head)
         C = n_head * D
         out = torch.empty(B, T, C, dtype=qkv.dtype, device=qkv.device)
+        if key_split is not None:
+            if workspace is None:
+                workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
+            name = "dlbb_attn_prefill_gqa_split" + ("_seq" if seq else "")
+            check(getattr(_lib.lib(), name)(qkv.data_ptr(), W, k_cache.data_ptr(),
+                                            v_cache.data_ptr(), length.data_ptr(),
+                                            workspace.data_ptr(), out.data_ptr(), C, B, T,
+                                            n_head, n_kv_head, D, L_max, bound, chunk,
+                                            1.0 / math.sqrt(D), _lib.stream(qkv.device)),
+                  name[5:])
+            return out
         name = "dlbb_attn_prefill_gqa" + ("_seq" if seq else "")
         check(getattr(_lib.lib(), name)(qkv.data_ptr(), W, k_cache.data_ptr(), v_cache.data_ptr(),
                                         length.data_ptr(), out.data_ptr(), C, B, T, n_head,

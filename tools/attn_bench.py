@@ -16,7 +16,12 @@ short chunk over a long prefix is where the halved cache stream can show); no SD
 ``--prefill --gqa``: the grouped-query kernel (``n_kv_head=``) at H_q 32, D 128, H_kv 8 / 4, T 8 /
 128 / 512, prefix 0 / 2048 / 8192, B 1 / 8, beside the ungrouped kernel on the cache repeated to
 32 heads and a copy of the grouped K + V bytes; median [min, max] over interleaved rounds (default
-``profiles/prefill_gqa/attn_prefill_gqa.jsonl``)."""
+``profiles/prefill_gqa/attn_prefill_gqa.jsonl``).
+
+``--prefill --gqa --split``: the same rows and candidates plus ``gqa_split``, the key-split form
+(``key_split=``) at ``CHUNK_PREFILL_GQA`` with its workspace allocated outside the timed region
+and ``len_bound`` = the live length; on the B 1 rows also at chunks 128 / 256 / 512 / 1024
+(``gqa_split_<chunk>``) (default ``profiles/prefill_gqa_split/attn_prefill_gqa_split.jsonl``)."""
 import argparse
 import json
 import os
@@ -128,14 +133,24 @@ def prefill_rows(out_path, fp8=False):
                         fh.flush()
 
 
-def prefill_gqa_rows(out_path, rounds=7):
+def prefill_gqa_rows(out_path, rounds=7, split=False):
     """Grouped-query chunked prefill at H_q 32, D 128: ``gqa`` (the grouped cache), ``expanded``
     (the ungrouped kernel on the cache repeated to 32 heads, built outside the timed region) and
     ``kv_copy`` (a device copy of the grouped K + V bytes read), one timed window of each per
-    round, round by round; per candidate the median, min and max over the rounds."""
+    round, round by round; per candidate the median, min and max over the rounds. ``split``: also
+    ``gqa_split`` (``key_split=CHUNK_PREFILL_GQA``, workspace allocated outside the timed region,
+    ``len_bound`` the live length) and, at B 1, ``gqa_split_<chunk>`` over the chunk sweep."""
     import statistics
 
-    from distributed_llm_backend_benchmark_amd.ops import kv_append, prefill_attention
+    from distributed_llm_backend_benchmark_amd.ops import (CHUNK_PREFILL_GQA, kv_append,
+                                                           prefill_attention,
+                                                           prefill_workspace_numel)
+
+    def split_fn(qkv, HKV, kc, vc, length, n, chunk):
+        B, T = qkv.shape[:2]
+        ws = torch.empty(prefill_workspace_numel(B, HQ, D, T, n, chunk), device="cuda")
+        return lambda: prefill_attention(qkv, HQ, kc, vc, length, n_kv_head=HKV, key_split=chunk,
+                                         len_bound=n, workspace=ws)
 
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -164,6 +179,15 @@ def prefill_gqa_rows(out_path, rounds=7):
                                "kv_copy": lambda: (kc.clone(), vc.clone())}
                         err = float((fns["gqa"]().float() - fns["expanded"]().float())
                                     .abs().max())
+                        if split:
+                            fns["gqa_split"] = split_fn(qkv, HKV, kc, vc, length, n,
+                                                        CHUNK_PREFILL_GQA)
+                            for ck in (128, 256, 512, 1024) if B == 1 else ():
+                                if ck != CHUNK_PREFILL_GQA:
+                                    fns[f"gqa_split_{ck}"] = split_fn(qkv, HKV, kc, vc, length,
+                                                                      n, ck)
+                            err_split = float((fns["gqa_split"]().float() - fns["gqa"]().float())
+                                              .abs().max())
                         # a timed window of >= 20 ms per candidate and round
                         iters = {k: max(10, min(2000, int(0.02 / t_best(fn, iters=5, rounds=1))))
                                  for k, fn in fns.items()}
@@ -179,6 +203,16 @@ def prefill_gqa_rows(out_path, rounds=7):
                                "kv_bytes_gqa": 2 * B * HKV * n * D * 2,
                                "kv_bytes_expanded": 2 * B * HQ * n * D * 2,
                                "gqa_over_expanded": med["gqa"] / med["expanded"]}
+                        if split:
+                            nck = -(-n // CHUNK_PREFILL_GQA)
+                            rec.update({"chunk": CHUNK_PREFILL_GQA,
+                                        "workgroups_gqa_split": rec["workgroups_gqa"] * nck,
+                                        "ws_bytes_gqa_split": 4 * prefill_workspace_numel(
+                                            B, HQ, D, T, n, CHUNK_PREFILL_GQA),
+                                        "max_abs_diff_gqa_split_vs_gqa": err_split,
+                                        "gqa_split_over_gqa": med["gqa_split"] / med["gqa"],
+                                        "gqa_split_over_expanded":
+                                            med["gqa_split"] / med["expanded"]})
                         for k, v in times.items():
                             rec.update({f"us_{k}": med[k], f"us_{k}_min": min(v),
                                         f"us_{k}_max": max(v)})
@@ -192,12 +226,15 @@ _ap.add_argument("--prefill", action="store_true")
 _ap.add_argument("--fp8", action="store_true", help="with --prefill: the FP8-cache rows")
 _ap.add_argument("--gqa", action="store_true",
                  help="with --prefill: the grouped-query kernel beside the expanded cache")
+_ap.add_argument("--split", action="store_true",
+                 help="with --prefill --gqa: the key-split form and its chunk sweep as well")
 _ap.add_argument("--out", default=None)
 _args = _ap.parse_args()
 if _args.prefill and _args.gqa:
+    _name = "prefill_gqa_split" if _args.split else "prefill_gqa"
     prefill_gqa_rows(_args.out or os.path.join(
-        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "prefill_gqa",
-        "attn_prefill_gqa.jsonl"))
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", _name,
+        f"attn_{_name}.jsonl"), split=_args.split)
     sys.exit(0)
 if _args.prefill:
     prefill_rows(_args.out or os.path.join(
