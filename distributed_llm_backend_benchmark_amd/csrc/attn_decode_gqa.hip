@@ -55,6 +55,18 @@
 //     barrier) and are merged in wave order; no atomics, no tickets: bit-identical from run to
 //     run. PerSeq changes only where L comes from, so row b of a ragged launch has the bits of a
 //     batch-1 shared-length launch at length[b].
+//
+// Sliding window (the Win instantiations, dlbb_attn_decode_gqa_win*): the query attends the last
+// W keys, itself included: rows [lo, L) with L as above and lo = max(0, L - W). The chunks are
+// laid from lo, not from 0: workgroup (c, kvh, b) owns [lo + c chunk, min(lo + (c + 1) chunk, L)),
+// n_chunks = ceil(min(len_bound, W) / chunk), the combine merges ceil((L - lo) / chunk) partials.
+// The grid, the live part of the workspace and the bytes read depend on the window, not on the
+// context length, and no row below lo is addressed. Contract: for a given (b, kvh, c, lo, L) the
+// workgroup does the arithmetic of the unwindowed kernel at (c, L - lo) on rows shifted by lo, in
+// the same order (K rows are loaded one by one and V rows by per-row DMA, so the shift costs no
+// alignment). With W >= L the result has the bits of the unwindowed launch at the same chunk;
+// when the window bites, those of an unwindowed launch on a cache holding keys [lo, L) at
+// positions 0 .. L - lo - 1.
 #include "attn_tile.h"
 #include "common.h"
 
@@ -116,6 +128,7 @@ struct GqaArgs {
   int64_t ld, ldo;
   int B, Hq, Hkv, G, L_max, chunk, n_chunks;
   float scale_log2;         // log2(e) * scale
+  int window;               // Win kernels: keys a query attends, 1 .. L_max
 };
 
 // keys row b attends: positions 0 .. min(len, L_max - 1) (the token was appended at `len`).
@@ -137,7 +150,12 @@ __device__ __forceinline__ int gqa_keys(const GqaArgs& a, int b, bool& empty) {
   return len < a.L_max ? len + 1 : a.L_max;
 }
 
-template <int D, bool PerSeq>
+// first key of a window of a.window keys that ends at L
+__device__ __forceinline__ int gqa_window_lo(const GqaArgs& a, int L) {
+  return L > a.window ? L - a.window : 0;
+}
+
+template <int D, bool PerSeq, bool Win>
 __global__ void __launch_bounds__(kGqaThreads, 2) attn_decode_gqa_split_kernel(GqaArgs a) {
   constexpr int ROW = 2 * D;                 // bytes of a V row
   constexpr int RPI = 1024 / ROW;            // rows per DMA wave-instruction
@@ -155,9 +173,11 @@ __global__ void __launch_bounds__(kGqaThreads, 2) attn_decode_gqa_split_kernel(G
   const int c = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
   bool empty;
   const int L = gqa_keys<PerSeq>(a, b, empty);
-  const int c0 = c * a.chunk;
-  if (c0 >= L) return;                       // dead chunk (every chunk of an empty slot): no K / V
+  int lo = 0;                                // Win: the chunks are laid from the window's first key
+  if constexpr (Win) lo = gqa_window_lo(a, L);
+  if (c * a.chunk >= L - lo) return;         // dead chunk (every chunk of an empty slot): no K / V
                                              // read, no partial written
+  const int c0 = lo + c * a.chunk;
   const int c1 = min(c0 + a.chunk, L);
   const int quarter = a.chunk / kGqaWaves;   // a multiple of kGqaStep (checked by the launcher)
   const int w0 = c0 + wave * quarter;        // this wave's keys [w0, w1); none when w1 <= w0
@@ -344,7 +364,7 @@ __global__ void __launch_bounds__(kGqaThreads, 2) attn_decode_gqa_split_kernel(G
 }
 
 // grid (H_q, B), D threads: thread d owns output column d of query head h
-template <int D, bool PerSeq>
+template <int D, bool PerSeq, bool Win>
 __global__ __launch_bounds__(D) void attn_decode_gqa_combine_kernel(GqaArgs a) {
   const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
   bool empty;
@@ -354,7 +374,9 @@ __global__ __launch_bounds__(D) void attn_decode_gqa_combine_kernel(GqaArgs a) {
     *op = 0;
     return;
   }
-  const int live = min((L + a.chunk - 1) / a.chunk, a.n_chunks);
+  int keys = L;                                    // Win: the chunks hold the window's keys only
+  if constexpr (Win) keys = L - gqa_window_lo(a, L);
+  const int live = min((keys + a.chunk - 1) / a.chunk, a.n_chunks);
   const float* p = a.ws + (static_cast<int64_t>(b) * a.Hq + h) * a.n_chunks * (D + 2);
   float mx = kGqaNegBig;
 #pragma unroll 4
@@ -406,11 +428,12 @@ int gqa_append_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
   return hipGetLastError();
 }
 
-template <bool PerSeq>
+// Win: `window` keys per query (>= 1, clamped to L_max: a window at or over L_max is no window)
+template <bool PerSeq, bool Win = false>
 int gqa_decode_launch(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache,
                       const void* length, void* ws, void* out, int64_t ldo, int B, int Hq,
                       int Hkv, int D, int L_max, int len_bound, int chunk, float scale,
-                      hipStream_t stream) {
+                      hipStream_t stream, int window = 0) {
   if (!gqa_range_ok(Hq, Hkv, D)) return hipErrorInvalidValue;
   if (B <= 0) return hipSuccess;
   if (!gqa_qkv_cache_ok(qkv, ld, k_cache, v_cache, length, Hq, Hkv, D, L_max))
@@ -419,21 +442,24 @@ int gqa_decode_launch(const void* qkv, int64_t ld, const void* k_cache, const vo
   if (!ws || mis(ws, 4) || !out || mis(out, 2) || ldo < static_cast<int64_t>(Hq) * D)
     return hipErrorInvalidValue;
   if (!(scale > 0.f) || Hq > 65535 || B > 65535) return hipErrorInvalidValue;
+  if (Win && window < 1) return hipErrorInvalidValue;
   if (len_bound > L_max) len_bound = L_max;
+  if (window > L_max) window = L_max;
+  if (Win && len_bound > window) len_bound = window;   // the grid covers the window's keys only
   const int n_chunks = (len_bound + chunk - 1) / chunk;
   GqaArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(k_cache),
             static_cast<const uint16_t*>(v_cache), static_cast<const int*>(length),
             static_cast<float*>(ws), static_cast<uint16_t*>(out), ld, ldo, B, Hq, Hkv, Hq / Hkv,
-            L_max, chunk, n_chunks, scale * 1.4426950408889634f};
+            L_max, chunk, n_chunks, scale * 1.4426950408889634f, window};
   const dim3 gs(n_chunks, Hkv, B), gc(Hq, B);
   if (D == 64) {
-    hipLaunchKernelGGL((attn_decode_gqa_split_kernel<64, PerSeq>), gs, dim3(kGqaThreads), 0,
+    hipLaunchKernelGGL((attn_decode_gqa_split_kernel<64, PerSeq, Win>), gs, dim3(kGqaThreads), 0,
                        stream, a);
-    hipLaunchKernelGGL((attn_decode_gqa_combine_kernel<64, PerSeq>), gc, dim3(64), 0, stream, a);
+    hipLaunchKernelGGL((attn_decode_gqa_combine_kernel<64, PerSeq, Win>), gc, dim3(64), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((attn_decode_gqa_split_kernel<128, PerSeq>), gs, dim3(kGqaThreads), 0,
+    hipLaunchKernelGGL((attn_decode_gqa_split_kernel<128, PerSeq, Win>), gs, dim3(kGqaThreads), 0,
                        stream, a);
-    hipLaunchKernelGGL((attn_decode_gqa_combine_kernel<128, PerSeq>), gc, dim3(128), 0, stream, a);
+    hipLaunchKernelGGL((attn_decode_gqa_combine_kernel<128, PerSeq, Win>), gc, dim3(128), 0, stream, a);
   }
   return hipGetLastError();
 }
@@ -489,4 +515,30 @@ DLBB_API int dlbb_attn_decode_gqa_seq(const void* qkv, int64_t ld, const void* k
                                       hipStream_t stream) {
   return gqa_decode_launch<true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B, Hq, Hkv, D,
                                  L_max, len_bound, chunk, scale, stream);
+}
+
+// Sliding window: dlbb_attn_decode_gqa with `window` >= 1 keys per query. Query head h attends
+// positions max(0, L - window) .. L - 1, L = min(*length, L_max - 1) + 1 (its own token
+// included); a window at or over L_max is no window. ws: fp32 [B, H_q, n_chunks, D + 2] with
+// n_chunks = ceil(min(len_bound, window, L_max) / chunk): the chunks are laid from the window's
+// first key, so the grid and the workspace do not grow with the context. window < 1 returns
+// hipErrorInvalidValue before any launch.
+DLBB_API int dlbb_attn_decode_gqa_win(const void* qkv, int64_t ld, const void* k_cache,
+                                      const void* v_cache, const void* length, void* ws,
+                                      void* out, int64_t ldo, int B, int Hq, int Hkv, int D,
+                                      int L_max, int len_bound, int chunk, int window,
+                                      float scale, hipStream_t stream) {
+  return gqa_decode_launch<false, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B, Hq,
+                                        Hkv, D, L_max, len_bound, chunk, scale, stream, window);
+}
+
+// The same with per-sequence lengths (dlbb_attn_decode_gqa_seq's rules): row b attends the last
+// `window` of its own length[b] + 1 keys.
+DLBB_API int dlbb_attn_decode_gqa_win_seq(const void* qkv, int64_t ld, const void* k_cache,
+                                          const void* v_cache, const void* length, void* ws,
+                                          void* out, int64_t ldo, int B, int Hq, int Hkv, int D,
+                                          int L_max, int len_bound, int chunk, int window,
+                                          float scale, hipStream_t stream) {
+  return gqa_decode_launch<true, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B, Hq,
+                                       Hkv, D, L_max, len_bound, chunk, scale, stream, window);
 }

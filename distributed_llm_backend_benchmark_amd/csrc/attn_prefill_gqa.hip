@@ -43,8 +43,24 @@
 //   * G is a launch argument (a shift), not a template parameter: the row mapping costs a few
 //     integer ops per lane outside the key loop, and the file keeps four instantiations
 //     (D x shared / per-sequence length).
+// Sliding window (the Win instantiations, dlbb_attn_prefill_gqa_win*): token i of row b attends the
+// last W keys, itself included: [max(0, len_b + i - W + 1), min(len_b + i, kend - 1)].
+//   * The tile loop starts at the block's first useful tile, floor(max(0, len_b + t0 - W + 1) /
+//     KB), from the block's FIRST token t0: workgroup-uniform, so every wave passes the same
+//     barriers of the double-buffered staging. Tiles below it are neither staged nor computed, so
+//     a short block over a long prefix walks the tiles of W + T keys and needs no key split.
+//   * The low side mirrors the high side. Per wave: wbot, the lower bound of its first token (a
+//     tile wholly below it is only staged), and wlow, that of its last token (a tile is masked on
+//     the low side only when it reaches below it). Per lane: the threshold
+//     max(0, len_b + token(lane) - W + 1) - k0 - 4 hi. Rows of a staged tile below a token's
+//     bound are live cache rows, masked by the score.
+//   * A row whose keys in a tile are all masked (its first visited tile can be, on the low side)
+//     has a tile max of -1e30 below the half-start running max: the max does not move, alpha = 1,
+//     p = 0. A token past the cache with no visible key ends with l = 0 and writes zeros.
+//   * With W >= len_b + T every bound is 0 and the launch has the bits of the unwindowed kernel.
 // Not here: a split of the keys across workgroups (a short block over a long prefix runs
-// H_kv B workgroups), paged and FP8 grouped caches.
+// H_kv B workgroups; under a window it visits the window's tiles only), paged and FP8 grouped
+// caches.
 #include "attn_tile.h"
 #include "common.h"
 
@@ -64,9 +80,10 @@ struct PrefillGqaArgs {
   int B, T, Hkv, L_max;
   int gsh;                  // log2 G
   float scale_log2;         // log2(e) * scale
+  int window;               // Win kernels: keys a token attends, >= 1
 };
 
-template <int D, bool PerSeq>
+template <int D, bool PerSeq, bool Win>
 __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(PrefillGqaArgs a) {
   using Geo = FwdGeo<D>;
   constexpr int KB = Geo::KB, ROW = Geo::ROW, RPI = Geo::RPI, TILE = Geo::TILE;
@@ -110,6 +127,23 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(Prefi
   const int64_t lw = static_cast<int64_t>(len) + tw;
   const int wlim = lw < kend - 1 ? static_cast<int>(lw) : kend - 1;
   const int64_t wtop = lw + NTW - 1;              // no key past it for any row of the wave
+  // Win: the low side. llo: first key of the lane's token; wbot / wlow: of the wave's first / last
+  // token (no row of the wave sees a key below wbot, none is masked at or above wlow); kt0: the
+  // tile holding the first key of the block's first token. A token past T takes the bound of token
+  // T - 1, so with a window over everything all four are 0 and no lane differs from the unwindowed
+  // kernel. Without a window they are the constant 0
+  int llo = 0, wbot = 0, wlow = 0, kt0 = 0;
+  if constexpr (Win) {
+    const int64_t last = static_cast<int64_t>(len) + a.T - 1;
+    auto low = [&](int64_t p) {                   // first key of the token at cache position p
+      const int64_t f = (p < last ? p : last) - a.window + 1;
+      return static_cast<int>(f < 0 ? 0 : f < kend ? f : kend);
+    };
+    llo = low(lq);
+    wbot = low(lw);
+    wlow = low(wtop);
+    kt0 = low(static_cast<int64_t>(len) + t0) / KB;
+  }
 
   // Q fragments (B operand of S^T = K Q^T), gathered: lane holds Q[tok][head][16 ks + 8 hi + j]
   bf16x8 qf[Geo::NKS];
@@ -152,8 +186,8 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(Prefi
     }
   };
 
-  stage(0, tileK(0), tileV(0));
-  for (int kt = 0; kt < nt; ++kt) {
+  if (!Win || kt0 < nt) stage(kt0 * KB, tileK(kt0 & 1), tileV(kt0 & 1));
+  for (int kt = kt0; kt < nt; ++kt) {
     const int cur = kt & 1;
     // one barrier per tile: it both publishes tile kt (every wave's DMA retired) and frees buffer
     // cur^1 (every wave finished tile kt-1), so the restage goes right after it
@@ -162,7 +196,7 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(Prefi
     if (kt + 1 < nt) stage((kt + 1) * KB, tileK(cur ^ 1), tileV(cur ^ 1));
     const int k0 = kt * KB;
     // wave-uniform: the wave has tokens and the tile a key one of them sees
-    if (wave_live && k0 <= wtop) {
+    if (wave_live && k0 <= wtop && k0 + KB > wbot) {
       const char* tk = tileK(cur);
       const char* tv = tileV(cur);
       // ---- S^T for the 32-key halves
@@ -189,6 +223,16 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(Prefi
 #pragma unroll
           for (int e = 0; e < 16; ++e)
             if (kk * 32 + (e & 3) + 8 * (e >> 2) > th) s[kk][e] = kPgNegBig;
+      }
+      if constexpr (Win) {
+        if (k0 < wlow) {                            // some key of the tile below the last token's
+          const int tl = llo - k0 - 4 * hi;         // window: the same key index, from below
+#pragma unroll
+          for (int kk = 0; kk < Geo::NKK; ++kk)
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+              if (kk * 32 + (e & 3) + 8 * (e >> 2) < tl) s[kk][e] = kPgNegBig;
+        }
       }
       float mx = kPgNegBig;                          // max of the RAW scores (scale > 0)
 #pragma unroll
@@ -266,11 +310,13 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(Prefi
 
 bool mis(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; }
 
-template <bool PerSeq>
+// Win: `window` keys per token (>= 1; one that covers every token's prefix is no window)
+template <bool PerSeq, bool Win = false>
 int prefill_gqa_launch(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache,
                        const void* length, void* out, int64_t ldo, int B, int T, int Hq, int Hkv,
-                       int D, int L_max, float scale, hipStream_t stream) {
+                       int D, int L_max, float scale, hipStream_t stream, int window = 0) {
   if (D != 64 && D != 128) return hipErrorInvalidValue;
+  if (Win && window < 1) return hipErrorInvalidValue;
   if (B <= 0 || T <= 0 || Hkv <= 0 || Hq <= 0 || L_max <= 0 || !(scale > 0.f))
     return hipErrorInvalidValue;
   if (Hq % Hkv) return hipErrorInvalidValue;
@@ -287,14 +333,14 @@ int prefill_gqa_launch(const void* qkv, int64_t ld, const void* k_cache, const v
   PrefillGqaArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(k_cache),
                    static_cast<const uint16_t*>(v_cache), static_cast<const int*>(length),
                    static_cast<uint16_t*>(out), ld, ldo, B, T, Hkv, L_max, gsh,
-                   scale * 1.4426950408889634f};
+                   scale * 1.4426950408889634f, window};
   const int TB = kQB >> gsh;                       // tokens per workgroup
   const dim3 grid((T + TB - 1) / TB, Hkv, B);
   if (D == 64)
-    hipLaunchKernelGGL((attn_prefill_gqa_kernel<64, PerSeq>), grid, dim3(kAttnThreads),
+    hipLaunchKernelGGL((attn_prefill_gqa_kernel<64, PerSeq, Win>), grid, dim3(kAttnThreads),
                        4 * FwdGeo<64>::TILE, stream, a);
   else
-    hipLaunchKernelGGL((attn_prefill_gqa_kernel<128, PerSeq>), grid, dim3(kAttnThreads),
+    hipLaunchKernelGGL((attn_prefill_gqa_kernel<128, PerSeq, Win>), grid, dim3(kAttnThreads),
                        4 * FwdGeo<128>::TILE, stream, a);
   return hipGetLastError();
 }
@@ -329,4 +375,26 @@ DLBB_API int dlbb_attn_prefill_gqa_seq(const void* qkv, int64_t ld, const void* 
                                        int L_max, float scale, hipStream_t stream) {
   return prefill_gqa_launch<true>(qkv, ld, k_cache, v_cache, length, out, ldo, B, T, Hq, Hkv, D,
                                   L_max, scale, stream);
+}
+
+// Sliding window: dlbb_attn_prefill_gqa with `window` >= 1 keys per token. Query i of head h
+// attends positions max(0, *length + i - window + 1) .. *length + i; the tiles below the first key
+// of a workgroup's first token are neither staged nor computed. window < 1 returns
+// hipErrorInvalidValue before any launch.
+DLBB_API int dlbb_attn_prefill_gqa_win(const void* qkv, int64_t ld, const void* k_cache,
+                                       const void* v_cache, const void* length, void* out,
+                                       int64_t ldo, int B, int T, int Hq, int Hkv, int D,
+                                       int L_max, int window, float scale, hipStream_t stream) {
+  return prefill_gqa_launch<false, true>(qkv, ld, k_cache, v_cache, length, out, ldo, B, T, Hq,
+                                         Hkv, D, L_max, scale, stream, window);
+}
+
+// The same with per-sequence lengths (dlbb_attn_prefill_gqa_seq's rules).
+DLBB_API int dlbb_attn_prefill_gqa_win_seq(const void* qkv, int64_t ld, const void* k_cache,
+                                           const void* v_cache, const void* length, void* out,
+                                           int64_t ldo, int B, int T, int Hq, int Hkv, int D,
+                                           int L_max, int window, float scale,
+                                           hipStream_t stream) {
+  return prefill_gqa_launch<true, true>(qkv, ld, k_cache, v_cache, length, out, ldo, B, T, Hq,
+                                        Hkv, D, L_max, scale, stream, window);
 }

@@ -241,8 +241,22 @@ _SIGS = {
     "dlbb_attn_prefill_gqa_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_float, c_void_p]),
-    # the same with the keys split over workgroups (csrc/attn_prefill_gqa_split.hip): ws before
-    # out, len_bound and chunk after L_max
+    # the sliding-window forms of the grouped-query decode and prefill: `window` before scale
+    "dlbb_attn_decode_gqa_win": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                         c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "dlbb_attn_decode_gqa_win_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                             c_int, c_int, c_int, c_int, c_int, c_float,
+                                             c_void_p]),
+    "dlbb_attn_prefill_gqa_win": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_int, c_float, c_void_p]),
+    "dlbb_attn_prefill_gqa_win_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                              c_int, c_int, c_int, c_float, c_void_p]),
+    # dlbb_attn_prefill_gqa with the keys split over workgroups (csrc/attn_prefill_gqa_split.hip):
+    # ws before out, len_bound and chunk after L_max
     "dlbb_attn_prefill_gqa_split": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_int, c_float,

@@ -144,8 +144,26 @@ Grouped-query heads (opt-in, ``n_kv_head=`` on :func:`kv_append` / :func:`decode
   merge is another fp32 order); bit-identical from run to run, a ragged row has the bits of its
   batch-1 shared-length launch at the same ``key_split`` and ``len_bound``. Nothing picks it by
   itself; the torch forms ignore ``key_split``.
+* ``window=W`` (opt-in, an int >= 1, on :func:`decode_attention` and :func:`prefill_attention`
+  with grouped heads; the ``dlbb_attn_decode_gqa_win*`` / ``dlbb_attn_prefill_gqa_win*`` entry
+  points) is sliding-window attention under the Mistral / HF ``sliding_window`` convention: a
+  query at cache position ``p`` attends keys ``max(0, p - W + 1) .. p``, the last ``W`` keys with
+  itself. The cache layout, the append, ``length``, ``len_bound``, ``pos``, the empty-slot and
+  ``L_max`` guards and both length forms keep their meaning; ``None`` is the calls above, launch
+  for launch. The decode split lays its chunks from the window's first key ``lo``: the grid, the
+  live workspace (:func:`workspace_numel` at ``min(len_bound, W)``; a :class:`KVCache` workspace
+  is always enough) and the K / V bytes read are those of a step over ``W`` keys at any context
+  length, and no row below ``lo`` is addressed. A window that bites has the bits of the unwindowed
+  step on a cache holding keys ``[lo, length]`` from position 0; one that covers the prefix has
+  the bits of the call without it. The one-launch prefill starts each workgroup at the tile
+  holding the first key of its first token and masks the low side per lane, so a short block over
+  a long prefix walks the tiles of ``W + T`` keys without a key split. The torch forms slice
+  (decode) or band-mask (prefill) the same keys. ``ValueError``: ``window < 1``, a window on
+  ungrouped heads, a window with ``key_split``.
 * Not built: paged and FP8 grouped caches (``ValueError``), an automatic choice between the split
-  and the one-launch prefill, a fused append, GQA in the models.
+  and the one-launch prefill, a fused append, GQA in the models; for the window: a rolling (ring)
+  cache that stores only ``W`` rows, attention sinks, a window on the ungrouped, paged, FP8 or
+  key-split kernels, any automatic choice of window.
 """
 
 from __future__ import annotations
@@ -621,6 +639,19 @@ def _kv_heads(n_head: int, n_kv_head: Optional[int]) -> Optional[int]:
     return n_kv_head
 
 
+def _window(what: str, window: Optional[int], n_kv_head: Optional[int]) -> Optional[int]:
+    """``window`` of a sliding-window call as an int, None for none; ``ValueError`` for a window
+    below one key or on ungrouped heads (``n_kv_head`` as :func:`_kv_heads` returned it)."""
+    if window is None:
+        return None
+    if int(window) < 1:
+        raise ValueError(f"{what}: window is a number of keys >= 1, got {window}")
+    if n_kv_head is None:
+        raise ValueError(f"{what}: the ungrouped kernels have no sliding window (window= goes "
+                         "with n_kv_head < n_head)")
+    return int(window)
+
+
 def _views_gqa(qkv: torch.Tensor, n_head: int, n_kv_head: int):
     """q ``[B, H_q, T, D]``, k / v ``[B, H_kv, T, D]`` views of the grouped layout ``[B, T,
     (H_q + 2 H_kv) * D]``: the query heads, then the key heads, then the value heads."""
@@ -658,18 +689,21 @@ def dequantize(cache: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 
 def torch_decode_attention(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
-                           v_scale=None, n_kv_head: Optional[int] = None) -> torch.Tensor:
+                           v_scale=None, n_kv_head: Optional[int] = None,
+                           window: Optional[int] = None) -> torch.Tensor:
     """Torch form of :func:`decode_attention` at the host position ``pos`` (not replayable
     across positions: the slice bound is a host value). ``n_kv_head``: the grouped layout; K / V
-    are expanded to the query heads with ``repeat_interleave`` for SDPA."""
+    are expanded to the query heads with ``repeat_interleave`` for SDPA. ``window`` (grouped
+    layout only): the keys are the slice ``[max(0, pos + 1 - window), pos + 1)``."""
     B, _, C3 = qkv.shape
     if n_kv_head is not None:
         torch_kv_append(qkv, n_head, k_cache, v_cache, pos, n_kv_head=n_kv_head)
         q, _, _ = _views_gqa(qkv, n_head, n_kv_head)
         G = n_head // n_kv_head
+        lo = 0 if window is None else max(0, pos + 1 - window)
         o = F.scaled_dot_product_attention(
-            q, k_cache[:, :, :pos + 1].repeat_interleave(G, dim=1),
-            v_cache[:, :, :pos + 1].repeat_interleave(G, dim=1))
+            q, k_cache[:, :, lo:pos + 1].repeat_interleave(G, dim=1),
+            v_cache[:, :, lo:pos + 1].repeat_interleave(G, dim=1))
         return o.transpose(1, 2).reshape(B, 1, n_head * q.shape[3])
     torch_kv_append(qkv, n_head, k_cache, v_cache, pos, k_scale, v_scale)
     q, _, _ = _views(qkv, n_head)
@@ -714,8 +748,8 @@ def torch_kv_append_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int], 
 
 
 def torch_decode_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int],
-                               k_scale=None, v_scale=None,
-                               n_kv_head: Optional[int] = None) -> torch.Tensor:
+                               k_scale=None, v_scale=None, n_kv_head: Optional[int] = None,
+                               window: Optional[int] = None) -> torch.Tensor:
     """Torch form of the per-sequence :func:`decode_attention` at the host positions ``pos``:
     row ``b`` is :func:`torch_decode_attention` on the batch-1 slice of its cache at ``pos[b]``,
     so a row has the bits of the shared-length form; empty slots give zero rows. (One SDPA over
@@ -730,7 +764,7 @@ def torch_decode_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence
         out[b:b + 1] = torch_decode_attention(
             qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p,
             None if k_scale is None else k_scale[b:b + 1],
-            None if v_scale is None else v_scale[b:b + 1], n_kv_head)
+            None if v_scale is None else v_scale[b:b + 1], n_kv_head, window)
     return out
 
 
@@ -989,23 +1023,30 @@ def _decode_attention_paged(qkv, n_head, k_pool, v_pool, length, len_bound, work
 
 def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
                             keep: Optional[torch.Tensor] = None, k_scale=None,
-                            v_scale=None, n_kv_head: Optional[int] = None) -> torch.Tensor:
+                            v_scale=None, n_kv_head: Optional[int] = None,
+                            window: Optional[int] = None) -> torch.Tensor:
     """Torch form of :func:`prefill_attention` at the host position ``pos``: fp32 SDPA of the
     ``T`` queries over ``cache[:, :, :pos + T]`` (the chunk already appended; an FP8 cache is
     dequantised with :func:`dequantize`) under an explicit bottom-right causal mask: query ``i``
     sees positions ``0 .. pos + i``. ``keep``: a boolean ``[pos + T]`` key mask on top (the paged
     form's unmapped pages); a key it removes has its K / V rows replaced by zeros, so nothing
     stale reaches the product. ``n_kv_head``: the grouped layout (the bf16 cache only); the live
-    cache rows are expanded to the query heads with ``repeat_interleave`` in fp32."""
+    cache rows are expanded to the query heads with ``repeat_interleave`` in fp32. ``window``
+    (grouped layout only): the band ``pos + i - window < key`` on top of the causal mask, over the
+    cache rows from the first token's bound on."""
     B, T, C3 = qkv.shape
     n = min(pos + T, k_cache.shape[2])
     mask = torch.ones(T, n, dtype=torch.bool, device=qkv.device).tril(diagonal=pos)
     if n_kv_head is not None:
         q, _, _ = _views_gqa(qkv, n_head, n_kv_head)
         G = n_head // n_kv_head
+        lo = 0                                  # rows below the first token's window: not read
+        if window is not None:
+            lo = max(0, pos - window + 1)
+            mask = mask.triu(diagonal=pos - window + 1)[:, lo:]
         o = F.scaled_dot_product_attention(
-            q.float(), k_cache[:, :, :n].float().repeat_interleave(G, 1),
-            v_cache[:, :, :n].float().repeat_interleave(G, 1), attn_mask=mask)
+            q.float(), k_cache[:, :, lo:n].float().repeat_interleave(G, 1),
+            v_cache[:, :, lo:n].float().repeat_interleave(G, 1), attn_mask=mask)
         return o.to(qkv.dtype).transpose(1, 2).reshape(B, T, n_head * q.shape[3])
     q, _, _ = _views(qkv, n_head)
     if k_scale is None:
@@ -1022,8 +1063,8 @@ def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
 
 
 def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int],
-                                k_scale=None, v_scale=None,
-                                n_kv_head: Optional[int] = None) -> torch.Tensor:
+                                k_scale=None, v_scale=None, n_kv_head: Optional[int] = None,
+                                window: Optional[int] = None) -> torch.Tensor:
     """Torch form of the per-sequence :func:`prefill_attention`: row ``b`` is
     :func:`torch_prefill_attention` on its batch-1 slice at ``pos[b]``; empty slots give zero
     rows."""
@@ -1035,7 +1076,7 @@ def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequenc
             out[b:b + 1] = torch_prefill_attention(
                 qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p, None,
                 None if k_scale is None else k_scale[b:b + 1],
-                None if v_scale is None else v_scale[b:b + 1], n_kv_head)
+                None if v_scale is None else v_scale[b:b + 1], n_kv_head, window)
     return out
 
 
@@ -1075,7 +1116,8 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                       v_scale: Optional[torch.Tensor] = None,
                       n_kv_head: Optional[int] = None, key_split: Optional[int] = None,
                       len_bound: Optional[int] = None,
-                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      workspace: Optional[torch.Tensor] = None,
+                      window: Optional[int] = None) -> torch.Tensor:
     """Chunked prefill (``csrc/attn_prefill.hip``): causal attention of a block of ``T`` new
     tokens over the cache, ``qkv [B, T, 3C]`` -> ``[B, T, C]``. The block's K / V must already be
     in the cache at ``[length, length + T)`` (:func:`kv_append`) and ``length`` not yet advanced;
@@ -1107,10 +1149,21 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     ``workspace``: fp32 partials of :func:`prefill_workspace_numel` elements at ``len_bound``
     (allocated per call when None; it needs no clearing). Same contract and bound as the unsplit
     kernel, not its bits; bit-identical from run to run. Nothing chooses the split by itself, and
-    the torch forms ignore it."""
+    the torch forms ignore it.
+
+    ``window`` (grouped heads only, not with ``key_split``; None = the whole prefix, call for
+    call): sliding-window attention (module docstring): query ``i`` attends the last ``window``
+    keys, itself included: positions ``max(0, length_b + i - window + 1) .. length_b + i``. The
+    one-launch kernel starts at the tile that holds the first key of a workgroup's first token,
+    so a short block over a long prefix costs the tiles of ``window + T`` keys. A window that
+    covers every token's prefix gives the bits of the call without one."""
     if qkv.dim() != 3 or qkv.shape[1] < 1:
         raise ValueError(f"prefill_attention takes qkv [B, T >= 1, 3C], got {tuple(qkv.shape)}")
     n_kv_head = _kv_heads(n_head, n_kv_head)
+    window = _window("prefill_attention", window, n_kv_head)
+    if window is not None and key_split is not None:
+        raise ValueError("prefill_attention: the key-split kernel has no window (window= goes "
+                         "with the one-launch kernel, which visits the window's tiles only)")
     if key_split is None and (len_bound is not None or workspace is not None):
         raise ValueError("prefill_attention: len_bound and workspace go with key_split")
     if key_split is not None:
@@ -1123,7 +1176,7 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     if n_kv_head is not None:
         _gqa_check("prefill_attention", k_cache, v_cache, k_scale, v_scale, block_table)
         return _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos,
-                                      key_split, len_bound, workspace)
+                                      key_split, len_bound, workspace, window)
     fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     B, T, C3 = qkv.shape
     C = C3 // 3
@@ -1229,9 +1282,10 @@ def _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos) -> Non
 
 
 def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_bound, workspace,
-                          pos, chunk, fused):
+                          pos, chunk, fused, window=None):
     """:func:`decode_attention` on the grouped layout: the GQA append launch, then the split over
-    the KV heads and the combine (``csrc/attn_decode_gqa.hip``)."""
+    the KV heads and the combine (``csrc/attn_decode_gqa.hip``); with ``window`` their ``_win``
+    entry points."""
     what = "decode_attention"
     if fused:
         raise ValueError(f"{what}: the grouped-query kernels have no fused append")
@@ -1253,19 +1307,23 @@ def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_
         bound = L_max if len_bound is None else max(1, min(int(len_bound), L_max))
         if host is not None and max(host) + 1 > bound:
             raise ValueError(f"{what}: position {max(host)} + 1 > len_bound {bound}")
-        need = workspace_numel(B, n_head, D, bound, chunk)
+        # under a window the chunks are laid from its first key: they cover min(bound, window) keys
+        need = workspace_numel(B, n_head, D, bound if window is None else min(bound, window),
+                               chunk)
         if workspace is None:
             workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
         elif workspace.numel() < need or workspace.dtype != torch.float32:
             raise ValueError(f"{what}: workspace of {workspace.numel()} fp32 < {need}")
         out = torch.empty(B, 1, C, dtype=qkv.dtype, device=qkv.device)
         _hip_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, 1)
-        name = "dlbb_attn_decode_gqa" + ("_seq" if seq else "")
+        name = "dlbb_attn_decode_gqa" + ("" if window is None else "_win") + \
+            ("_seq" if seq else "")
+        win = () if window is None else (min(window, L_max),)
         check(getattr(_lib.lib(), name)(qkv.data_ptr(), qkv.shape[2], k_cache.data_ptr(),
                                         v_cache.data_ptr(), length.data_ptr(),
                                         workspace.data_ptr(), out.data_ptr(), C, B, n_head,
-                                        n_kv_head, D, L_max, bound, chunk, 1.0 / math.sqrt(D),
-                                        _lib.stream(qkv.device)), name[5:])
+                                        n_kv_head, D, L_max, bound, chunk, *win,
+                                        1.0 / math.sqrt(D), _lib.stream(qkv.device)), name[5:])
         return out
     if host is None:
         host = _host_positions(length, None) if seq else [_host_pos(length, None)]
@@ -1273,17 +1331,19 @@ def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_
             raise ValueError(f"{what}: position {max(host)} + 1 > cache length {L_max}")
     if seq:
         return torch_decode_attention_seq(qkv, n_head, k_cache, v_cache, host,
-                                          n_kv_head=n_kv_head)
-    return torch_decode_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head)
+                                          n_kv_head=n_kv_head, window=window)
+    return torch_decode_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head,
+                                  window=window)
 
 
 def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos,
-                           key_split=None, len_bound=None, workspace=None):
+                           key_split=None, len_bound=None, workspace=None, window=None):
     """:func:`prefill_attention` on the grouped layout: one launch of
     ``csrc/attn_prefill_gqa.hip``, whose workgroups take the (token, query head) rows of one KV
     head, so a K / V tile is staged once for the ``G`` heads sharing it. With ``key_split`` (a
     chunk in keys, checked by the caller) the split and combine launches of
-    ``csrc/attn_prefill_gqa_split.hip`` instead."""
+    ``csrc/attn_prefill_gqa_split.hip`` instead; with ``window`` (never both) the ``_win`` entry
+    points of the one-launch kernel."""
     what = "prefill_attention"
     B, T, W = qkv.shape
     L_max = k_cache.shape[2]
@@ -1318,10 +1378,12 @@ def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos
                                             1.0 / math.sqrt(D), _lib.stream(qkv.device)),
                   name[5:])
             return out
-        name = "dlbb_attn_prefill_gqa" + ("_seq" if seq else "")
+        name = "dlbb_attn_prefill_gqa" + ("" if window is None else "_win") + \
+            ("_seq" if seq else "")
+        win = () if window is None else (min(window, 2 ** 31 - 1),)     # a C int
         check(getattr(_lib.lib(), name)(qkv.data_ptr(), W, k_cache.data_ptr(), v_cache.data_ptr(),
                                         length.data_ptr(), out.data_ptr(), C, B, T, n_head,
-                                        n_kv_head, D, L_max, 1.0 / math.sqrt(D),
+                                        n_kv_head, D, L_max, *win, 1.0 / math.sqrt(D),
                                         _lib.stream(qkv.device)), name[5:])
         return out
     if host is None:
@@ -1330,8 +1392,9 @@ def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos
             raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
     if seq:
         return torch_prefill_attention_seq(qkv, n_head, k_cache, v_cache, host,
-                                           n_kv_head=n_kv_head)
-    return torch_prefill_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head)
+                                           n_kv_head=n_kv_head, window=window)
+    return torch_prefill_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head,
+                                   window=window)
 
 
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
@@ -1400,7 +1463,8 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                      v_scale: Optional[torch.Tensor] = None,
                      block_table: Optional[torch.Tensor] = None, table_host=None,
                      max_len: Optional[int] = None,
-                     n_kv_head: Optional[int] = None) -> torch.Tensor:
+                     n_kv_head: Optional[int] = None,
+                     window: Optional[int] = None) -> torch.Tensor:
     """One decode step of causal attention: ``qkv [B, 1, 3C]`` -> ``[B, 1, C]``; the token's
     K / V are stored at cache position ``length`` and the query attends over ``length + 1``
     keys. ``length`` is not advanced.
@@ -1426,14 +1490,23 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     ``qkv`` is ``[B, 1, (n_head + 2 n_kv_head) * D]``, the caches hold ``n_kv_head`` heads and
     query head ``h`` attends KV head ``h // (n_head // n_kv_head)``; the contract above holds.
     The chunk default is :data:`CHUNK_GQA`; there is no fused append (an append launch, then the
-    split and the combine), and no paged or FP8 form yet (``ValueError``)."""
+    split and the combine), and no paged or FP8 form yet (``ValueError``).
+
+    ``window`` (grouped heads only; None = the whole prefix, call for call): sliding-window
+    attention (module docstring): the query attends the last ``window`` keys, its own token
+    included: positions ``max(0, length + 1 - window) .. length``. The split's chunks are laid
+    from the window's first key, so the grid, the K / V bytes read and the workspace needed
+    (:func:`workspace_numel` at ``min(len_bound, window)``) are those of a step over ``window``
+    keys at any context length. A window at or over ``length + 1`` gives the bits of the call
+    without one."""
     if qkv.dim() != 3 or qkv.shape[1] != 1:
         raise ValueError(f"decode_attention takes qkv [B, 1, 3C], got {tuple(qkv.shape)}")
     n_kv_head = _kv_heads(n_head, n_kv_head)
+    window = _window("decode_attention", window, n_kv_head)
     if n_kv_head is not None:
         _gqa_check("decode_attention", k_cache, v_cache, k_scale, v_scale, block_table)
         return _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_bound,
-                                     workspace, pos, chunk, fused)
+                                     workspace, pos, chunk, fused, window)
     if block_table is not None:
         return _decode_attention_paged(qkv, n_head, k_cache, v_cache, length, len_bound,
                                        workspace, pos, chunk, fused, k_scale, v_scale,

@@ -21,7 +21,12 @@ short chunk over a long prefix is where the halved cache stream can show); no SD
 ``--prefill --gqa --split``: the same rows and candidates plus ``gqa_split``, the key-split form
 (``key_split=``) at ``CHUNK_PREFILL_GQA`` with its workspace allocated outside the timed region
 and ``len_bound`` = the live length; on the B 1 rows also at chunks 128 / 256 / 512 / 1024
-(``gqa_split_<chunk>``) (default ``profiles/prefill_gqa_split/attn_prefill_gqa_split.jsonl``)."""
+(``gqa_split_<chunk>``) (default ``profiles/prefill_gqa_split/attn_prefill_gqa_split.jsonl``).
+
+``--prefill --gqa --window W``: the sliding-window form (``window=W``): T 8 / 128 over a prefix of
+8192 keys, ``gqa_window`` beside the unwindowed one-launch kernel (``gqa``), the key-split kernel
+(``gqa_split``), ``expanded`` and ``kv_copy_window``, a copy of the ``W + T`` K + V rows the window
+spans (default ``profiles/gqa_window/attn_prefill_gqa_window.jsonl``)."""
 import argparse
 import json
 import os
@@ -133,18 +138,21 @@ def prefill_rows(out_path, fp8=False):
                         fh.flush()
 
 
-def prefill_gqa_rows(out_path, rounds=7, split=False):
+def prefill_gqa_rows(out_path, rounds=7, split=False, window=None):
     """Grouped-query chunked prefill at H_q 32, D 128: ``gqa`` (the grouped cache), ``expanded``
     (the ungrouped kernel on the cache repeated to 32 heads, built outside the timed region) and
     ``kv_copy`` (a device copy of the grouped K + V bytes read), one timed window of each per
     round, round by round; per candidate the median, min and max over the rounds. ``split``: also
     ``gqa_split`` (``key_split=CHUNK_PREFILL_GQA``, workspace allocated outside the timed region,
-    ``len_bound`` the live length) and, at B 1, ``gqa_split_<chunk>`` over the chunk sweep."""
+    ``len_bound`` the live length) and, at B 1, ``gqa_split_<chunk>`` over the chunk sweep.
+    ``window``: the rows of a short block over a long prefix only, with ``gqa_split`` (no sweep),
+    ``gqa_window`` (``window=``; checked against the torch form) and ``kv_copy_window``."""
     import statistics
 
     from distributed_llm_backend_benchmark_amd.ops import (CHUNK_PREFILL_GQA, kv_append,
                                                            prefill_attention,
                                                            prefill_workspace_numel)
+    from distributed_llm_backend_benchmark_amd.ops.decode import torch_prefill_attention
 
     def split_fn(qkv, HKV, kc, vc, length, n, chunk):
         B, T = qkv.shape[:2]
@@ -159,8 +167,8 @@ def prefill_gqa_rows(out_path, rounds=7, split=False):
         for HKV in (8, 4):
             G = HQ // HKV
             for B in (1, 8):
-                for T in (8, 128, 512):
-                    for prefix in (0, 2048, 8192):
+                for T in (8, 128) if window else (8, 128, 512):
+                    for prefix in (8192,) if window else (0, 2048, 8192):
                         n = prefix + T
                         qkv = torch.randn(B, T, (HQ + 2 * HKV) * D, device="cuda",
                                           generator=gen).bfloat16()
@@ -179,10 +187,20 @@ def prefill_gqa_rows(out_path, rounds=7, split=False):
                                "kv_copy": lambda: (kc.clone(), vc.clone())}
                         err = float((fns["gqa"]().float() - fns["expanded"]().float())
                                     .abs().max())
-                        if split:
+                        if window:
+                            lo = max(0, prefix - window + 1)
+                            fns["gqa_window"] = lambda: prefill_attention(
+                                qkv, HQ, kc, vc, length, n_kv_head=HKV, window=window)
+                            fns["kv_copy_window"] = lambda: (kc[:, :, lo:].clone(),
+                                                             vc[:, :, lo:].clone())
+                            want = torch_prefill_attention(qkv, HQ, kc, vc, prefix, n_kv_head=HKV,
+                                                           window=window)
+                            err_window = float((fns["gqa_window"]().float() - want.float())
+                                               .abs().max())
+                        if split or window:
                             fns["gqa_split"] = split_fn(qkv, HKV, kc, vc, length, n,
                                                         CHUNK_PREFILL_GQA)
-                            for ck in (128, 256, 512, 1024) if B == 1 else ():
+                            for ck in (128, 256, 512, 1024) if B == 1 and not window else ():
                                 if ck != CHUNK_PREFILL_GQA:
                                     fns[f"gqa_split_{ck}"] = split_fn(qkv, HKV, kc, vc, length,
                                                                       n, ck)
@@ -203,7 +221,17 @@ def prefill_gqa_rows(out_path, rounds=7, split=False):
                                "kv_bytes_gqa": 2 * B * HKV * n * D * 2,
                                "kv_bytes_expanded": 2 * B * HQ * n * D * 2,
                                "gqa_over_expanded": med["gqa"] / med["expanded"]}
-                        if split:
+                        if window:
+                            KB = 8192 // (2 * D)                # keys per tile of the kernel
+                            rec.update({"window": window,
+                                        "tiles_gqa": -(-n // KB), "tiles_gqa_window":
+                                            -(-n // KB) - lo // KB,
+                                        "kv_bytes_window": 2 * B * HKV * (n - lo) * D * 2,
+                                        "max_abs_diff_gqa_window_vs_torch": err_window,
+                                        "gqa_window_over_gqa": med["gqa_window"] / med["gqa"],
+                                        "gqa_window_over_gqa_split":
+                                            med["gqa_window"] / med["gqa_split"]})
+                        if split or window:
                             nck = -(-n // CHUNK_PREFILL_GQA)
                             rec.update({"chunk": CHUNK_PREFILL_GQA,
                                         "workgroups_gqa_split": rec["workgroups_gqa"] * nck,
@@ -228,13 +256,17 @@ _ap.add_argument("--gqa", action="store_true",
                  help="with --prefill: the grouped-query kernel beside the expanded cache")
 _ap.add_argument("--split", action="store_true",
                  help="with --prefill --gqa: the key-split form and its chunk sweep as well")
+_ap.add_argument("--window", type=int, default=None,
+                 help="with --prefill --gqa: the sliding-window form over a prefix of 8192 keys")
 _ap.add_argument("--out", default=None)
 _args = _ap.parse_args()
 if _args.prefill and _args.gqa:
     _name = "prefill_gqa_split" if _args.split else "prefill_gqa"
+    _dir = "gqa_window" if _args.window else _name
     prefill_gqa_rows(_args.out or os.path.join(
-        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", _name,
-        f"attn_{_name}.jsonl"), split=_args.split)
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", _dir,
+        f"attn_{'prefill_gqa_window' if _args.window else _name}.jsonl"), split=_args.split,
+        window=_args.window)
     sys.exit(0)
 if _args.prefill:
     prefill_rows(_args.out or os.path.join(

@@ -50,6 +50,13 @@ heads (``G`` times the bytes), ``copy`` a device copy of the K + V bytes the gro
 read, ``gqa_chunk<N>`` the kernel at the other ``--gqa-chunks``. ``GBps`` is over the bytes each
 candidate reads; ``gqa_over_expanded`` stands beside ``one_over_G``, what the byte counts alone
 would give; ``us_min`` / ``us_max`` are the spread over the rounds.
+
+``--gqa --window W`` times the sliding-window step (``window=W``) instead, same rows, to
+``profiles/gqa_window/attn_decode_gqa_window.jsonl``: ``window`` at context ``L`` beside ``full``
+(the unwindowed step at ``L``), ``short`` (the unwindowed step at context ``W`` on the same caches:
+the same keys per workgroup, the time the windowed step should take) and ``copy_window`` (a copy
+of the window's K + V rows). The caches rotate by the window's bytes. ``window_over_short`` stands
+beside ``short_spread``, the min and max round of ``short`` over its median.
 """
 
 from __future__ import annotations
@@ -513,6 +520,80 @@ def bench_gqa_row(B, HQ, KV, D, L, args):
                                               / ref.abs().max())}
 
 
+def bench_gqa_window_row(B, HQ, KV, D, L, args):
+    """``--gqa --window W``: the windowed step at context ``L`` (``window``) beside the unwindowed
+    step at context ``L`` (``full``), the unwindowed step at context ``W`` on the same caches
+    (``short``: the same chunks of keys per workgroup, so the time ``window`` should take) and a
+    strided device copy of the window's K + V rows (``copy_window``)."""
+    import torch
+
+    from distributed_llm_backend_benchmark_amd.ops import decode as dec
+
+    dev = torch.device("cuda", 0)
+    W = min(args.window, L)
+    win_bytes = 2 * B * KV * W * D * 2                   # what the windowed kernel must read
+    # rotate by the WINDOW's bytes: the full caches are larger, the windowed step reads this much
+    nbuf = max(1, min(16, -(-args.rotate_mb * (1 << 20) // win_bytes)))
+    g = torch.Generator(device=dev).manual_seed(L + HQ + KV)
+    caches = [torch.randn(2, B, KV, L, D, generator=g, device=dev).to(torch.bfloat16)
+              for _ in range(nbuf)]
+    sink = torch.empty(2, B, KV, W, D, dtype=torch.bfloat16, device=dev)
+    qkv = torch.randn(B, 1, (HQ + 2 * KV) * D, generator=g, device=dev).to(torch.bfloat16)
+    at_L = torch.tensor([L - 1], dtype=torch.int32, device=dev)
+    at_W = torch.tensor([W - 1], dtype=torch.int32, device=dev)
+    ws = torch.empty(dec.workspace_numel(B, HQ, D, L, dec.CHUNK_GQA), dtype=torch.float32,
+                     device=dev)
+
+    def step(i, length, **kw):
+        kc, vc = caches[i % nbuf]
+        return dec.decode_attention(qkv, HQ, kc, vc, length, workspace=ws, n_kv_head=KV, **kw)
+
+    cands = {"window": lambda i: step(i, at_L, window=W), "full": lambda i: step(i, at_L),
+             "short": lambda i: step(i, at_W, len_bound=W),
+             "copy_window": lambda i: sink.copy_(caches[i % nbuf][:, :, :, L - W:])}
+    graphs = {}
+    for name, fn in cands.items():                       # warm every candidate, then capture
+        for i in range(nbuf + 1):
+            fn(i)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(args.inner):
+                fn(i)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    times = {n: [] for n in graphs}
+    for _ in range(args.rounds):                         # alternate the candidates
+        for name, gr in graphs.items():
+            # an untimed replay first: `window` and `short` are compared to a few percent, and
+            # each is then timed behind its own traffic, not behind its neighbour's in this loop
+            gr.replay()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            gr.replay()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.inner)
+    us = {n: statistics.median(v) for n, v in times.items()}
+    ref = dec.torch_decode_attention(qkv, HQ, *caches[0], L - 1, n_kv_head=KV, window=W).float()
+    ratio = us["window"] / us["short"]
+    spread = [min(times["short"]) / us["short"], max(times["short"]) / us["short"]]
+    return {"B": B, "H_q": HQ, "H_kv": KV, "G": HQ // KV, "D": D, "L": L, "window": W,
+            "window_kv_bytes": win_bytes, "full_kv_bytes": win_bytes // W * L,
+            "rotated_caches": nbuf, "chunk_gqa": dec.CHUNK_GQA, "inner": args.inner,
+            "rounds": args.rounds, "us": us, "us_min": {n: min(v) for n, v in times.items()},
+            "us_max": {n: max(v) for n, v in times.items()},
+            "workgroups": {"window": -(-W // dec.CHUNK_GQA) * KV * B,
+                           "full": -(-L // dec.CHUNK_GQA) * KV * B},
+            "window_GBps": win_bytes / (us["window"] * 1e-6) / 1e9,
+            "window_over_full": us["window"] / us["full"], "window_over_short": ratio,
+            "short_spread": spread, "within_short_spread": bool(ratio <= spread[1]),
+            "share_of_copy": win_bytes / us["window"] / (2 * win_bytes / us["copy_window"]),
+            "max_rel_diff_vs_torch": float((cands["window"](0).float() - ref).abs().max()
+                                           / ref.abs().max())}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -520,6 +601,9 @@ def main(argv=None) -> int:
                     help="time grouped-query decode instead: gqa, expanded, copy, gqa_chunk<N>; "
                          "--rows are then B,H_q,H_kv,D,L")
     ap.add_argument("--gqa-chunks", type=int, nargs="*", default=[256, 512, 1024])
+    ap.add_argument("--window", type=int, default=None,
+                    help="with --gqa: the sliding-window step instead: window, full, short "
+                         "(the unwindowed step at context W), copy_window")
     ap.add_argument("--rows", nargs="*", default=None, metavar="B,H,D,L")
     ap.add_argument("--chunks", type=int, nargs="*", default=[128, 256, 512])
     ap.add_argument("--fp8", action="store_true",
@@ -540,7 +624,9 @@ def main(argv=None) -> int:
                          "profiles/ragged_decode/attn_decode_ragged.jsonl)")
     args = ap.parse_args(argv)
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", *(("gqa_decode", "attn_decode_gqa.jsonl")
+        args.out = os.path.join(REPO, "profiles", *(("gqa_window", "attn_decode_gqa_window.jsonl")
+                                                    if args.gqa and args.window else
+                                                    ("gqa_decode", "attn_decode_gqa.jsonl")
                                                     if args.gqa else
                                                     ("paged_decode", "attn_decode_paged.jsonl")
                                                     if args.paged else
@@ -551,7 +637,20 @@ def main(argv=None) -> int:
             else GQA_ROWS if args.gqa else DEFAULT_ROWS)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
-        for shape in rows if args.gqa else ():
+        for shape in rows if args.gqa and args.window else ():
+            row = bench_gqa_window_row(*shape, args)
+            f.write(json.dumps(row) + "\n")
+            f.flush()
+            print("B={} H_q={} H_kv={} D={} L={} W={} ({:.0f} MiB K+V in the window, {} caches): "
+                  .format(*shape, row["window"], row["window_kv_bytes"] / 2**20,
+                          row["rotated_caches"]) +
+                  "  ".join(f"{n} {t:.1f} us [{row['us_min'][n]:.1f}, {row['us_max'][n]:.1f}]"
+                            for n, t in row["us"].items()) +
+                  f"  window/short {row['window_over_short']:.3f} (short spread "
+                  f"{row['short_spread'][0]:.3f} .. {row['short_spread'][1]:.3f})"
+                  f"  window/full {row['window_over_full']:.3f}"
+                  f"  share_of_copy {row['share_of_copy']:.2f}", flush=True)
+        for shape in rows if args.gqa and not args.window else ():
             row = bench_gqa_row(*shape, args)
             f.write(json.dumps(row) + "\n")
             f.flush()
