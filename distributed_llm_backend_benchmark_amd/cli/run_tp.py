@@ -27,6 +27,9 @@ one e8m0 scale per 32 k; ``ops.mxfp4``) the same way: suffix ``_decode<N>_w4``. 
 codes with one fp32 scale per cached row (``ops.decode``): suffix ``_kv8`` (after ``_w8`` / ``_w4``), the
 ``decode`` section carries ``kv_dtype`` and counts codes + scales in its cache and K / V bytes. It
 composes with ``--decode-weights fp8`` / ``mxfp4`` and needs decode tokens and a real attention (not ``slice``).
+``--kv-cache mxfp4`` keeps it as MXFP4 (e2m1 codes with one e8m0 scale per 32 columns of a cached
+row; ``ops.decode``) under the same rules: suffix ``_kv4`` in ``_kv8``'s place; it is refused with
+``--kv-page-size`` and ``--prefill-chunk``.
 ``--prompt-lens L0,L1,...`` (``execution.prompt_lengths``) makes the batch right-padded prompts of
 these lengths over a per-sequence KV cache (``ops.decode``): one value per batch row in ``[1,
 sequence_length]``; needs decode tokens and a real attention, composes with ``--kv-cache fp8`` and
@@ -130,11 +133,12 @@ def parse_args(argv=None):
                          "output file gets the suffix _w8; mxfp4 = e2m1 codes with one e8m0 "
                          "scale per 32 k on the weight-only MXFP4 skinny GEMM, the same limits, "
                          "suffix _w4")
-    ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default=None,
+    ap.add_argument("--kv-cache", choices=["bf16", "fp8", "mxfp4"], default=None,
                     help="with --decode: storage of the KV cache (execution.kv_cache_dtype): fp8 = "
                          "e4m3 codes with one fp32 scale per cached row, head_dim + 4 bytes per "
                          "row instead of 2 head_dim; not with attention slice (no cache); output "
-                         "file gets the suffix _kv8")
+                         "file gets the suffix _kv8; mxfp4 = e2m1 codes with one e8m0 scale per "
+                         "32 columns (suffix _kv4; not with --kv-page-size / --prefill-chunk)")
     ap.add_argument("--prompt-lens", default=None, metavar="L0,L1,...",
                     help="with --decode: the batch is right-padded prompts of these lengths "
                          "(execution.prompt_lengths), one per batch row in [1, sequence_length], "
@@ -221,10 +225,11 @@ def main(argv=None) -> int:
     if args.kv_cache:
         ex["kv_cache_dtype"] = args.kv_cache
     kv8 = ex.get("kv_cache_dtype", "bf16") == "fp8"
-    if kv8 and (not n_dec or ex.get("attention", "slice") == "slice"):
+    kv4 = ex.get("kv_cache_dtype", "bf16") == "mxfp4"
+    if (kv8 or kv4) and (not n_dec or ex.get("attention", "slice") == "slice"):
         # refused before any process group exists: nothing to quantise, never a silent bf16 run
         if os.environ.get("RANK", "0") == "0":
-            print("ERROR: --kv-cache fp8 (execution.kv_cache_dtype) needs " +
+            print(f"ERROR: --kv-cache {ex['kv_cache_dtype']} (execution.kv_cache_dtype) needs " +
                   ("decode tokens (--decode N): only the decode steps keep a KV cache"
                    if not n_dec else
                    "attention sdpa or flash: attention slice keeps no K / V to quantise"))
@@ -297,6 +302,9 @@ def main(argv=None) -> int:
         elif page not in KV_PAGE_SIZES:
             why = (f"--kv-page-size (execution.kv_page_size) must be one of {KV_PAGE_SIZES}, "
                    f"got {page}")
+        elif kv4:
+            why = ("--kv-page-size (execution.kv_page_size) needs a bf16 or fp8 KV cache: a paged "
+                   "MXFP4 cache is not built")
         else:
             # positions every row ends at: what the pool has to hold
             row_tokens = [v + n_dec
@@ -630,7 +638,7 @@ def main(argv=None) -> int:
             suffix += f"_{extra['gemm_dtype']}"
         if dec is not None:                    # never overwrites the prefill record
             suffix += f"_decode{n_dec}" + ("_w8" if w8 else "_w4" if w4 else "") + \
-                ("_kv8" if kv8 else "") + ("_ragged" if lens else "") + \
+                ("_kv8" if kv8 else "_kv4" if kv4 else "") + ("_ragged" if lens else "") + \
                 (f"_paged{page}" if page else "") + (f"_chunk{pchunk}" if pchunk else "")
             d = results["decode"]
             print(f"  decode: {d['ms_per_token_mean']:.4f} ms/token ({d['timing_mode']}, "
@@ -640,7 +648,7 @@ def main(argv=None) -> int:
                    "per step)" if w8 else "") +
                   (f" ({d['weight_dtype']} weights, {d['w4_launches_per_step']} W4 launches "
                    "per step)" if w4 else "") +
-                  (f" ({d['kv_dtype']} KV cache)" if kv8 else ""))
+                  (f" ({d['kv_dtype']} KV cache)" if kv8 or kv4 else ""))
         out = os.path.join(config["experiment"]["output_dir"],
                            f"{args.backend}_{config['experiment']['name']}{suffix}.json")
         save_results(results, out, rank)
@@ -687,8 +695,9 @@ class _DecodeRunner:
             self.attention_path = "hip"
         else:
             self.attention_path = "torch"
-        # bytes of one cached position: K + V rows of hd bf16, or of hd e4m3 codes + an fp32 scale
-        row_bytes = hd + 4 if cache.kv_dtype == "fp8" else 2 * hd
+        # bytes of one cached position: K + V rows of hd bf16, of hd e4m3 codes + an fp32 scale, or
+        # of hd / 2 bytes of e2m1 pairs + hd / 32 e8m0 bytes
+        row_bytes = {"fp8": hd + 4, "mxfp4": hd // 2 + hd // 32}.get(cache.kv_dtype, 2 * hd)
         self.kv_per_key = cache.num_layers * cache.batch * heads * row_bytes * 2
         self.x = torch.empty(batch.shape[0], 1, batch.shape[2], dtype=batch.dtype,
                              device=batch.device)

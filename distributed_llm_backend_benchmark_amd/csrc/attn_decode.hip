@@ -1,5 +1,5 @@
-// Single-query (decode) attention over a KV cache, bf16 or FP8 (OCP e4m3fn), gfx950 (MI355X,
-// CDNA4).
+// Single-query (decode) attention over a KV cache, bf16, FP8 (OCP e4m3fn) or MXFP4 (OCP MX: e2m1
+// codes, e8m0 block scales), gfx950 (MI355X, CDNA4).
 //
 // Cache layout, per layer and rank: k_cache / v_cache [B, H, L_max, D], contiguous, so the key
 // stream of one (b, h) is one contiguous run; `length` is ONE device int32 = tokens already
@@ -63,6 +63,45 @@
 // FP8 codes are widened in registers (v_cvt_pk_f32_fp8, exact); the dot product runs on the raw
 // codes, the key's scale is folded into the score (s = dot * k_scale * scale_log2) and the
 // value's into the weight (o += (p * v_scale) * code, l += p).
+//
+// MXFP4 cache (ops.mxfp4 is the specification of the format and of the quantiser; contiguous
+// caches only). k_cache / v_cache [B, H, L_max, D / 2] bytes, element 2j of a row in the low nibble
+// of byte j; k_scale / v_scale [B, H, L_max, D / 32] e8m0 bytes, one per 32 consecutive columns,
+// meaning 2^(b - 127); no fp32 row scale. A row is D / 2 + D / 32 bytes (68 at D = 128). The
+// kernels are their own (kv_append_mxfp4_kernel, attn_decode_mxfp4_kernel), not instantiations of
+// the core below, whose schedule is left alone; the combine kernel, the workspace, `length`,
+// `len_bound`, `fused` and the dead-chunk / empty-slot rules are shared.
+//   * Quantiser (append and fused append): per block of 32, b = clamp(exponent(amax) - 2, 2, 254)
+//     from the exponent field of amax (127 when amax == 0), the multiply by 2^(127 - b) is exact,
+//     clamp to 6, round half even on the grid step (0.5 below 2, 1 below 4, 2 above), sign bit
+//     exactly when x < 0: the bits of gemm_mxfp4.hip's row quantiser and of mxfp4._quantize_rows.
+//   * Append: a lane owns ONE MX block: 32 consecutive columns of a row (b, t, k|v, h), four
+//     16-byte loads, amax / scale / 16 code bytes without any cross-lane step, one 16-byte store
+//     and one scale byte. Lanes are laid block-fastest over (b, t, k|v, h, block), the order of
+//     qkv itself: the 64 lanes of a wave read one contiguous 4 KiB run of qkv (each load
+//     instruction takes 16 of a lane's 64 bytes, the four together use every line whole), and the
+//     D / 32 lanes of a row store its D / 2 code bytes and D / 32 scale bytes contiguously. Rows
+//     of different heads are L_max rows apart in the cache, so no order makes the stores of a
+//     wave one run for T = 1; the loads carry 4x the bytes and get the contiguous order.
+//   * Split: a lane's fragment is 16 codes (an 8-byte load), D / 16 lanes per key, two lanes per
+//     scale byte: the FP8 kernel's slot geometry (32 key slots per workgroup at D = 128, 64 at
+//     D = 64). The 32-code fragment (one whole MX block per lane, a 16-byte load, no shared scale)
+//     was built and measured at D = 128: 170 VGPRs and 2 waves per SIMD against 110 and 4, and
+//     1.2-1.9x the time on every row (docs/PERFORMANCE.md, "Decode: MXFP4 KV cache"); at D = 64 it
+//     would be 128 slots, 512 keys a trip over a 256-key chunk. Each lane loads the one scale
+//     byte of its block (one byte load per row and lane: the lanes of a key cover the row's 4 or
+//     2 bytes).
+//   * Widening: v_cvt_scalef32_pk_f32_fp4 with the block's 2^(b - 127) (the float whose bits are
+//     b << 23) as its scale operand: a power of two, so the fp32 result is the exact dequantised
+//     element and the scale costs no VALU. K's scale is therefore applied per lane BEFORE the
+//     cross-lane reduction of the dot product (the blocks of a key carry different scales), V's the
+//     same way, and l += p stays unscaled.
+//   * Fused append: every slot of the chunk owning `length` quantises its fragment's columns of
+//     the token from qkv in registers (one xor-1 shuffle joins the amax of the two lanes of a
+//     block), slot 0 stores codes and scale bytes, and the loop takes row
+//     `length` from those registers: attention over the cache contents after the append, exactly.
+//   * Rows at or past L are never read (masked slots re-read row k1 - 1), so a scale byte 0xFF
+//     there (inf as a float) cannot reach a result.
 //
 // `fused` = 1: the chunk that owns position `length` takes the new token's K / V from `qkv` and
 // also writes them to the cache, so append + attend is one launch; 0: the caller appended first
@@ -572,6 +611,286 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_split_kernel(DecodeAr
   }
 }
 
+// ---- MXFP4 cache (file header) --------------------------------------------------------------
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// the e8m0 byte of a block from its amax: clamp(floor(log2 amax) - 2 + 127, 2, 254), the floor
+// from the exponent field (a subnormal amax lies below every scale the clamp allows)
+__device__ __forceinline__ uint32_t e8m0_byte(float amax) {
+  int b = static_cast<int>(__float_as_uint(amax) >> 23) - 2;
+  b = b < 2 ? 2 : (b > 254 ? 254 : b);
+  return amax == 0.f ? 127u : static_cast<uint32_t>(b);
+}
+
+// gemm_mxfp4.hip's rounding: `inv` = 2^(127 - b), the product is exact
+__device__ __forceinline__ uint32_t e2m1_nibble(float x, float inv) {
+  const float a = __builtin_fminf(__builtin_fabsf(x) * inv, 6.0f);
+  const float c = a < 2.0f ? __builtin_rintf(a * 2.0f)
+                           : (a < 4.0f ? __builtin_rintf(a) + 2.0f : __builtin_rintf(a * 0.5f) + 4.0f);
+  return static_cast<uint32_t>(c) | (x < 0.0f ? 8u : 0u);
+}
+
+// a lane's fragment of a cached row: C codes in C / 2 bytes
+template <int C> struct Mx4Frag;
+template <> struct Mx4Frag<32> { using T = u32x4; };
+template <> struct Mx4Frag<16> { using T = u32x2; };
+
+// C bf16 columns at p (inside one MX block) -> floats and their amax
+template <int C>
+__device__ __forceinline__ float mx4_load_cols(const uint16_t* p, float (&f)[C]) {
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < C / 8; ++i) {
+    const u16x8 x = *reinterpret_cast<const u16x8*>(p + 8 * i);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      f[8 * i + j] = bf16_to_f32(x[j]);
+      amax = __builtin_fmaxf(amax, __builtin_fabsf(f[8 * i + j]));
+    }
+  }
+  return amax;
+}
+
+// the codes of C columns under the block's scale byte b
+template <int C>
+__device__ __forceinline__ typename Mx4Frag<C>::T mx4_codes(const float (&f)[C], uint32_t b) {
+  const float inv = __uint_as_float((254u - b) << 23);
+  typename Mx4Frag<C>::T code;
+#pragma unroll
+  for (int i = 0; i < C / 8; ++i) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w |= e2m1_nibble(f[8 * i + j], inv) << (4 * j);
+    code[i] = w;
+  }
+  return code;
+}
+
+// C codes under scale byte b -> the C dequantised elements, exactly (b << 23 is 2^(b - 127))
+template <int C>
+__device__ __forceinline__ void mx4_widen(const typename Mx4Frag<C>::T& r, uint32_t b,
+                                          float (&v)[C]) {
+  const float s = __uint_as_float(b << 23);
+#pragma unroll
+  for (int i = 0; i < C / 8; ++i) {
+    const f32x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r[i], s, 0);
+    const f32x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r[i], s, 1);
+    const f32x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r[i], s, 2);
+    const f32x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r[i], s, 3);
+    v[8 * i] = p0[0];
+    v[8 * i + 1] = p0[1];
+    v[8 * i + 2] = p1[0];
+    v[8 * i + 3] = p1[1];
+    v[8 * i + 4] = p2[0];
+    v[8 * i + 5] = p2[1];
+    v[8 * i + 6] = p3[0];
+    v[8 * i + 7] = p3[1];
+  }
+}
+
+struct KvAppend4Args {
+  const uint16_t* qkv;   // [B, T, 3, H, D], token row stride ld
+  uint8_t* k_cache;      // [B, H, L_max, D / 2] e2m1 pairs
+  uint8_t* v_cache;
+  uint8_t* k_scale;      // [B, H, L_max, D / 32] e8m0
+  uint8_t* v_scale;
+  const int* length;
+  int64_t ld;
+  int B, T, H, L_max;
+};
+
+// one MX block (b, t, k|v, h, block) per thread step, block fastest (file header)
+template <int D, bool PerSeq>
+__global__ __launch_bounds__(256) void kv_append_mxfp4_kernel(KvAppend4Args a) {
+  constexpr int NB = D / 32;                                // blocks (= scale bytes) per row
+  [[maybe_unused]] const int len0 = PerSeq ? 0 : *a.length;
+  const int64_t per_tok = 2LL * a.H * NB;
+  const int64_t total = static_cast<int64_t>(a.B) * a.T * per_tok;
+  const int64_t step = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+       i += step) {
+    const int64_t tok = i / per_tok;
+    const int r = static_cast<int>(i - tok * per_tok);      // (k|v, h, block)
+    const int b = static_cast<int>(tok / a.T), t = static_cast<int>(tok - (int64_t)b * a.T);
+    const int kv = r / (a.H * NB);
+    const int hb = r - kv * a.H * NB;                       // h * NB + block
+    const int h = hb / NB, blk = hb - h * NB;
+    int len;
+    if constexpr (PerSeq) len = a.length[b];
+    else len = len0;
+    const int64_t pos = static_cast<int64_t>(len) + t;
+    if (len < 0 || pos >= a.L_max) continue;                // device-side guard: never past the cache
+    float f[32];
+    const float amax = mx4_load_cols<32>(
+        a.qkv + tok * a.ld + static_cast<int64_t>(1 + kv) * a.H * D + hb * 32, f);
+    const uint32_t sb = e8m0_byte(amax);
+    const int64_t row = (static_cast<int64_t>(b) * a.H + h) * a.L_max + pos;
+    *reinterpret_cast<u32x4*>((kv ? a.v_cache : a.k_cache) + row * (D / 2) + blk * 16) =
+        mx4_codes<32>(f, sb);
+    (kv ? a.v_scale : a.k_scale)[row * NB + blk] = static_cast<uint8_t>(sb);
+  }
+}
+
+// the split kernel over the MXFP4 cache: attn_decode_split_kernel's grid, partials and rules
+template <int D, bool PerSeq>
+__global__ __launch_bounds__(kDecThreads) void attn_decode_mxfp4_kernel(DecodeArgs a) {
+  constexpr int C = 16;                      // codes per lane: half an MX block (file header)
+  using Frag = typename Mx4Frag<C>::T;
+  constexpr int LPK = D / C;                 // lanes per key
+  constexpr int NS = kDecThreads / LPK;      // key slots per workgroup
+  constexpr int NB = D / 32;                 // scale bytes per row
+  constexpr int U = kDecUnroll;
+  __shared__ float red[kDecThreads / kWave][D + 2];
+
+  const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  int len;
+  bool room;
+  const int L = decode_keys<PerSeq>(a, b, len, room);
+  const int k0 = c * a.chunk;
+  if (k0 >= L) return;                       // dead chunk (every chunk of an empty slot)
+  const int k1 = min(k0 + a.chunk, L);
+  const int tid = threadIdx.x, sub = tid % LPK, slot = tid / LPK;
+  const int newpos = (a.fused && room) ? len : -1;
+
+  const uint16_t* row = a.qkv + static_cast<int64_t>(b) * a.ld + h * D + sub * C;
+  float q[C];                                // the lane's C columns of the query
+  mx4_load_cols<C>(row, q);
+  const int64_t rows = (static_cast<int64_t>(b) * a.H + h) * a.L_max;
+  // the lane's bytes of row 0 of (b, h), and the scale byte of its block
+  uint8_t* kc = a.k_cache + rows * (D / 2) + sub * (C / 2);
+  uint8_t* vc = a.v_cache + rows * (D / 2) + sub * (C / 2);
+  uint8_t* ksc = reinterpret_cast<uint8_t*>(a.k_scale) + rows * NB + sub * C / 32;
+  uint8_t* vsc = reinterpret_cast<uint8_t*>(a.v_scale) + rows * NB + sub * C / 32;
+
+  // the append, by the chunk owning `length` (workgroup-uniform): every slot holds the token's
+  // codes and scale bytes, slot 0 stores them
+  Frag nk{}, nv{};
+  uint32_t nkb = 127, nvb = 127;
+  if (newpos >= k0 && newpos < k1) {
+    float f[C];
+    float amax = mx4_load_cols<C>(row + a.H * D, f);
+    amax = __builtin_fmaxf(amax, __shfl_xor(amax, 1, 64));   // lanes sub, sub ^ 1: one block
+    nkb = e8m0_byte(amax);
+    nk = mx4_codes<C>(f, nkb);
+    amax = mx4_load_cols<C>(row + 2 * a.H * D, f);
+    amax = __builtin_fmaxf(amax, __shfl_xor(amax, 1, 64));
+    nvb = e8m0_byte(amax);
+    nv = mx4_codes<C>(f, nvb);
+    if (slot == 0) {
+      *reinterpret_cast<Frag*>(kc + static_cast<int64_t>(newpos) * (D / 2)) = nk;
+      *reinterpret_cast<Frag*>(vc + static_cast<int64_t>(newpos) * (D / 2)) = nv;
+      if (sub * C % 32 == 0) {
+        ksc[static_cast<int64_t>(newpos) * NB] = static_cast<uint8_t>(nkb);
+        vsc[static_cast<int64_t>(newpos) * NB] = static_cast<uint8_t>(nvb);
+      }
+    }
+  }
+
+  float m = kDecNegBig, l = 0.f, o[C];
+#pragma unroll
+  for (int j = 0; j < C; ++j) o[j] = 0.f;
+
+  for (int it = k0; it < k1; it += NS * U) {       // uniform trip count over the workgroup
+    Frag kr[U], vr[U];
+    uint32_t ks[U], vs[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int key = it + u * NS + slot;
+      ok[u] = key < k1;
+      const int kk = ok[u] ? key : k1 - 1;         // masked slots re-read a live row
+      const bool fresh = kk == newpos;
+      // row `newpos` is taken from the registers, never from what the loads return for it (slot
+      // 0's stores may or may not have landed): the loads stay in bounds, kk < L <= L_max
+      const Frag kl = *reinterpret_cast<const Frag*>(kc + static_cast<int64_t>(kk) * (D / 2));
+      const Frag vl = *reinterpret_cast<const Frag*>(vc + static_cast<int64_t>(kk) * (D / 2));
+      const uint32_t ksl = ksc[static_cast<int64_t>(kk) * NB];
+      const uint32_t vsl = vsc[static_cast<int64_t>(kk) * NB];
+      kr[u] = fresh ? nk : kl;
+      vr[u] = fresh ? nv : vl;
+      ks[u] = fresh ? nkb : ksl;
+      vs[u] = fresh ? nvb : vsl;
+    }
+    float s[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float kf[C];
+      mx4_widen<C>(kr[u], ks[u], kf);
+      float d = 0.f;
+#pragma unroll
+      for (int j = 0; j < C; ++j) d = __builtin_fmaf(q[j], kf[j], d);
+#pragma unroll
+      for (int off = 1; off < LPK; off <<= 1) d += __shfl_xor(d, off, 64);
+      s[u] = ok[u] ? d * a.scale_log2 : kDecNegBig;
+    }
+    float mn = m;
+#pragma unroll
+    for (int u = 0; u < U; ++u) mn = fmaxf(mn, s[u]);
+    const float alpha = __builtin_amdgcn_exp2f(m - mn);
+    l *= alpha;
+#pragma unroll
+    for (int j = 0; j < C; ++j) o[j] *= alpha;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const float p = ok[u] ? __builtin_amdgcn_exp2f(s[u] - mn) : 0.f;
+      float vf[C];
+      mx4_widen<C>(vr[u], vs[u], vf);
+      l += p;
+#pragma unroll
+      for (int j = 0; j < C; ++j) o[j] = __builtin_fmaf(p, vf[j], o[j]);
+    }
+    m = mn;
+  }
+
+  // the merges of attn_decode_split_kernel: the slots of a wave by a butterfly whose two sides
+  // round identically, then the 4 waves through LDS in wave order
+#pragma unroll
+  for (int off = LPK; off < kWave; off <<= 1) {
+    const float m2 = __shfl_xor(m, off, 64), l2 = __shfl_xor(l, off, 64);
+    const float mn = fmaxf(m, m2);
+    const float f1 = __builtin_amdgcn_exp2f(m - mn), f2 = __builtin_amdgcn_exp2f(m2 - mn);
+    const bool lo = (tid & off) == 0;
+    const float la = lo ? l * f1 : l2 * f2, lb = lo ? l2 * f2 : l * f1;
+    l = la + lb;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+      const float o2 = __shfl_xor(o[j], off, 64);
+      const float oa = lo ? o[j] * f1 : o2 * f2, ob = lo ? o2 * f2 : o[j] * f1;
+      o[j] = oa + ob;
+    }
+    m = mn;
+  }
+  const int lane = tid & (kWave - 1), w = tid / kWave;
+  if (lane < LPK) {
+#pragma unroll
+    for (int j = 0; j < C; ++j) red[w][sub * C + j] = o[j];
+    if (sub == 0) {
+      red[w][D] = m;
+      red[w][D + 1] = l;
+    }
+  }
+  __syncthreads();
+  if (tid < D) {
+    float mw = red[0][D];
+#pragma unroll
+    for (int i = 1; i < kDecThreads / kWave; ++i) mw = fmaxf(mw, red[i][D]);
+    float lw = 0.f, ow = 0.f;
+#pragma unroll
+    for (int i = 0; i < kDecThreads / kWave; ++i) {
+      const float f = __builtin_amdgcn_exp2f(red[i][D] - mw);
+      lw = __builtin_fmaf(red[i][D + 1], f, lw);
+      ow = __builtin_fmaf(red[i][tid], f, ow);
+    }
+    float* p = a.ws + ((static_cast<int64_t>(b) * a.H + h) * a.n_chunks + c) * (D + 2);
+    p[2 + tid] = ow;
+    if (tid == 0) {
+      p[0] = mw;
+      p[1] = lw;
+    }
+  }
+}
+
 // grid (H, B), D threads: thread d owns output column d of head h
 template <int D, bool PerSeq>
 __global__ __launch_bounds__(D) void attn_decode_combine_kernel(DecodeArgs a) {
@@ -637,6 +956,14 @@ bool paged_ok(const PageTable& t, int L_max, int chunk, int& psh) {
   return true;
 }
 
+// the MXFP4 cache as decode_launch's format: its split kernel is attn_decode_mxfp4_kernel, its
+// scale planes are bytes (no alignment to ask for)
+struct KvMx4 {
+  static constexpr bool kScaled = true;
+};
+template <typename Fmt> constexpr bool kIsMx4 = false;
+template <> constexpr bool kIsMx4<KvMx4> = true;
+
 // validation and the split + combine launches of the decode entry points
 template <typename Fmt, bool PerSeq, bool Paged = false>
 int decode_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, void* k_scale,
@@ -648,7 +975,8 @@ int decode_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, voi
   if (PerSeq && !seq_length_ok(length)) return hipErrorInvalidValue;
   if (chunk <= 0 || len_bound <= 0 || !ws || ldo < H * D) return hipErrorInvalidValue;
   if (!k_cache || !v_cache || !out) return hipErrorInvalidValue;
-  if (Fmt::kScaled && !scales_ok(k_scale, v_scale)) return hipErrorInvalidValue;
+  if (kIsMx4<Fmt> ? !(k_scale && v_scale) : Fmt::kScaled && !scales_ok(k_scale, v_scale))
+    return hipErrorInvalidValue;
   if (H > 65535 || B > 65535) return hipErrorInvalidValue;
   int psh = 0;
   if (Paged && !paged_ok(pt, L_max, chunk, psh)) return hipErrorInvalidValue;
@@ -661,7 +989,18 @@ int decode_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, voi
                n_chunks, fused ? 1 : 0, scale * 1.4426950408889634f,
                static_cast<const int*>(pt.table), pt.stride, pt.n_pages, psh};
   const dim3 gs(n_chunks, H, B), gc(H, B);
-  if (D == 64) {
+  if constexpr (kIsMx4<Fmt>) {
+    static_assert(!Paged, "no paged MXFP4 cache");
+    if (D == 64) {
+      hipLaunchKernelGGL((attn_decode_mxfp4_kernel<64, PerSeq>), gs, dim3(kDecThreads), 0,
+                         stream, a);
+      hipLaunchKernelGGL((attn_decode_combine_kernel<64, PerSeq>), gc, dim3(64), 0, stream, a);
+    } else {
+      hipLaunchKernelGGL((attn_decode_mxfp4_kernel<128, PerSeq>), gs, dim3(kDecThreads), 0,
+                         stream, a);
+      hipLaunchKernelGGL((attn_decode_combine_kernel<128, PerSeq>), gc, dim3(128), 0, stream, a);
+    }
+  } else if (D == 64) {
     hipLaunchKernelGGL((attn_decode_split_kernel<64, Fmt, PerSeq, Paged>), gs, dim3(kDecThreads),
                        0, stream, a);
     hipLaunchKernelGGL((attn_decode_combine_kernel<64, PerSeq>), gc, dim3(64), 0, stream, a);
@@ -713,6 +1052,28 @@ int append_fp8_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
     hipLaunchKernelGGL((kv_append_fp8_kernel<64, PerSeq, Paged>), grid, dim3(256), 0, stream, a);
   else
     hipLaunchKernelGGL((kv_append_fp8_kernel<128, PerSeq, Paged>), grid, dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// the same for the MXFP4 append entry points
+template <bool PerSeq>
+int append_mxfp4_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache, void* k_scale,
+                        void* v_scale, const void* length, int B, int T, int H, int D, int L_max,
+                        hipStream_t stream) {
+  if (B <= 0 || T <= 0 || H <= 0) return hipSuccess;
+  if (!qkv_cache_ok(qkv, ld, k_cache, v_cache, length, H, D, L_max)) return hipErrorInvalidValue;
+  if (PerSeq && !seq_length_ok(length)) return hipErrorInvalidValue;
+  if (!k_cache || !v_cache || !k_scale || !v_scale) return hipErrorInvalidValue;
+  KvAppend4Args a{static_cast<const uint16_t*>(qkv), static_cast<uint8_t*>(k_cache),
+                  static_cast<uint8_t*>(v_cache), static_cast<uint8_t*>(k_scale),
+                  static_cast<uint8_t*>(v_scale), static_cast<const int*>(length), ld, B, T, H,
+                  L_max};
+  const int64_t lanes = static_cast<int64_t>(B) * T * 2 * H * (D / 32);
+  const dim3 grid(stream_grid(lanes, 256));
+  if (D == 64)
+    hipLaunchKernelGGL((kv_append_mxfp4_kernel<64, PerSeq>), grid, dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL((kv_append_mxfp4_kernel<128, PerSeq>), grid, dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -802,6 +1163,41 @@ DLBB_API int dlbb_attn_decode_fp8_seq(const void* qkv, int64_t ld, void* k_cache
                                       hipStream_t stream) {
   return decode_launch<KvE4m3, true>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, ws, out,
                                      ldo, B, H, D, L_max, len_bound, chunk, fused, scale, stream);
+}
+
+// The MXFP4 cache (file header): k_cache / v_cache [B, H, L_max, D / 2] bytes, k_scale / v_scale
+// [B, H, L_max, D / 32] e8m0 bytes, all contiguous; the contracts of the _fp8 entry points
+// otherwise.
+DLBB_API int dlbb_kv_append_mxfp4(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                  void* k_scale, void* v_scale, const void* length, int B, int T,
+                                  int H, int D, int L_max, hipStream_t stream) {
+  return append_mxfp4_launch<false>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, B, T, H,
+                                    D, L_max, stream);
+}
+
+DLBB_API int dlbb_kv_append_mxfp4_seq(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                      void* k_scale, void* v_scale, const void* length, int B,
+                                      int T, int H, int D, int L_max, hipStream_t stream) {
+  return append_mxfp4_launch<true>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, B, T, H,
+                                   D, L_max, stream);
+}
+
+DLBB_API int dlbb_attn_decode_mxfp4(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                    void* k_scale, void* v_scale, const void* length, void* ws,
+                                    void* out, int64_t ldo, int B, int H, int D, int L_max,
+                                    int len_bound, int chunk, int fused, float scale,
+                                    hipStream_t stream) {
+  return decode_launch<KvMx4, false>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, ws, out,
+                                     ldo, B, H, D, L_max, len_bound, chunk, fused, scale, stream);
+}
+
+DLBB_API int dlbb_attn_decode_mxfp4_seq(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                        void* k_scale, void* v_scale, const void* length,
+                                        void* ws, void* out, int64_t ldo, int B, int H, int D,
+                                        int L_max, int len_bound, int chunk, int fused,
+                                        float scale, hipStream_t stream) {
+  return decode_launch<KvMx4, true>(qkv, ld, k_cache, v_cache, k_scale, v_scale, length, ws, out,
+                                    ldo, B, H, D, L_max, len_bound, chunk, fused, scale, stream);
 }
 
 // The paged forms (file header): k_pool / v_pool [n_pages, H, P, D] (FP8: k_scale / v_scale

@@ -27,7 +27,9 @@ codes, one e8m0 scale per 32 k — K/2 + K/32 bytes per row). Both copies are re
 + 26.6 % weight memory.
 ``kv_cache_dtype="fp8"`` (opt-in) makes ``new_kv_cache`` hold e4m3 codes with one fp32 scale per
 cached row (``ops.decode``): the appends quantise, a decode step attends to the quantised rows, the
-prefill attention itself stays on the bf16 ``qkv``.
+prefill attention itself stays on the bf16 ``qkv``. ``kv_cache_dtype="mxfp4"`` (opt-in) holds e2m1
+codes with one e8m0 scale per 32 columns of a cached row under the same rules (``head_dim / 2 +
+head_dim / 32`` bytes a row; contiguous caches only, no chunked prefill).
 """
 
 from __future__ import annotations
@@ -246,8 +248,8 @@ class LLM(nn.Module):
                  overlap_chunks: int = 1, gemm_dtype: str = "bf16",
                  decode_weight_dtype: str = "bf16", kv_cache_dtype: str = "bf16"):
         super().__init__()
-        if kv_cache_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"kv_cache_dtype must be bf16|fp8, got {kv_cache_dtype!r}")
+        if kv_cache_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"kv_cache_dtype must be bf16|fp8|mxfp4, got {kv_cache_dtype!r}")
         self.kv_cache_dtype = kv_cache_dtype
         self.gemm_dtype = gemm_dtype
         self.decode_weight_dtype = _check_decode_weight_dtype(decode_weight_dtype, gemm_dtype)
@@ -295,7 +297,7 @@ class LLM(nn.Module):
         With ``decode_weight_dtype="fp8"`` on the HIP path the batch is the M of the W8 skinny
         GEMM (``"mxfp4"``: of the W4 one): more than 16 rows raise here, not in the middle of a
         step. ``kv_cache_dtype`` picks the cache's storage (``"fp8"``: e4m3 codes + one fp32
-        scale per row). ``per_sequence=True``: one length per batch row (``ops.decode``), for a
+        scale per row; ``"mxfp4"``: e2m1 codes + one e8m0 byte per 32 columns, contiguous only). ``per_sequence=True``: one length per batch row (``ops.decode``), for a
         batch whose sequences differ in length; see :meth:`forward`. ``page_size`` (with
         ``n_pages``, default: a page for every position of every row): a PAGED cache
         (``ops.decode``): one pool of ``n_pages`` pages of ``page_size`` positions per layer,

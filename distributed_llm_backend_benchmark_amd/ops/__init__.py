@@ -11,7 +11,8 @@
 * :mod:`.optim` — flat fused AdamW.
 * :mod:`.clip` — global gradient-norm clipping: bucket sum-of-squares, device-side coefficient.
 * :mod:`.xent` — fused softmax cross-entropy on bf16 logits; LM-head-fused linear + loss.
-* :mod:`.decode` — KV cache (bf16, or opt-in e4m3 codes with one fp32 scale per row), append, and
+* :mod:`.decode` — KV cache (bf16, or opt-in e4m3 codes with one fp32 scale per row, or opt-in
+  MXFP4: e2m1 codes with one e8m0 scale per 32 columns; ``CHUNK_MXFP4`` in :mod:`.decode`), append, and
   single-query (decode) attention split over the keys; chunked prefill (``prefill_attention``):
   causal attention of a block of new tokens over the cache; grouped-query decode and chunked
   prefill (``n_kv_head=``): one K / V read per KV head for the query heads sharing it, on MFMA.

@@ -185,6 +185,19 @@ _SIGS = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                          c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                          c_void_p]),
+    # the MXFP4 cache (uint8 codes and e8m0 scale bytes): the signatures of the _fp8 four
+    "dlbb_kv_append_mxfp4": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dlbb_kv_append_mxfp4_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         c_void_p]),
+    "dlbb_attn_decode_mxfp4": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                       c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "dlbb_attn_decode_mxfp4_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                           c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                           c_void_p]),
     # paged pools (block_table, its row stride, n_pages, P after `length`)
     "dlbb_kv_append_paged": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -46,6 +46,30 @@ head dim 64 / 128 and contiguous bf16 ``qkv``; the torch forms otherwise (the ap
 with ``fp8._quantize_torch``, the decode dequantises ``cache[:, :, :pos + 1]`` to fp32 and runs
 SDPA).
 
+MXFP4 cache (opt-in, ``KVCache(kv_dtype="mxfp4")``; the same file's ``attn_decode_mxfp4_kernel``
+and ``kv_append_mxfp4_kernel``, kernels of their own beside the shared core). The contract:
+
+* ``k_cache`` / ``v_cache`` are ``[B, H_local, L_max, D/2]`` ``uint8``, contiguous: byte ``j`` of a
+  row holds element ``2j`` in its low nibble and ``2j+1`` in its high nibble, e2m1 codes (the
+  layout of :mod:`.mxfp4`). ``k_scale`` / ``v_scale`` are ``[B, H_local, L_max, D/32]`` ``uint8``,
+  contiguous: one e8m0 byte ``b`` per 32 consecutive columns of a row, meaning ``2^(b-127)``.
+  There is no fp32 row scale: pure MX. ``D % 32 == 0``; a fresh cache holds scale bytes 127.
+* A row is quantised exactly as ``mxfp4._quantize_rows`` quantises a row of ``D`` values (the
+  reference, compared bit for bit; :mod:`.mxfp4` states the rule).
+* A row stores ``D/2 + D/32`` bytes: 68 at D = 128 against 132 (FP8) and 256 (bf16), 34 at 64:
+  0.515 of the FP8 cache, 0.266 of bf16.
+* The FP8 cache's rules hold: a decode step stores the token QUANTISED and attends to it in that
+  form, a replayed graph gives the eager bits, ``length`` / ``len_bound`` / the workspace / the
+  combine step and both length forms keep their meaning; the split runs in chunks of
+  :data:`CHUNK_MXFP4` keys. Rows at or past the live length are never read, whatever they hold.
+* :func:`kv_append` / :func:`decode_attention` recognise the form by ``uint8`` caches of width
+  ``D/2`` with ``uint8`` scales of width ``D/32`` in ``k_scale`` / ``v_scale``. HIP on a GPU tensor
+  with head dim 64 / 128 and contiguous bf16 ``qkv``; the torch forms otherwise (the append
+  quantises with ``mxfp4._quantize_rows``, the decode dequantises ``cache[:, :, :pos + 1]`` by the
+  rule of ``mxfp4.dequantize_mxfp4`` and runs SDPA).
+* Not built (``ValueError``): a paged MXFP4 cache, :func:`prefill_attention` over one, grouped-query
+  heads with one; the models' chunked prefill keeps requiring the bf16 cache.
+
 Per-sequence lengths (opt-in, ``KVCache(per_sequence=True)``; the ``*_seq`` entry points, the same
 kernel templates with ``length[b]`` in place of ``*length``). The contract:
 
@@ -178,6 +202,7 @@ from . import _lib
 from ._lib import check, use_hip
 from .attention import HEAD_DIMS, _views
 from .fp8 import E4M3, _quantize_torch
+from .mxfp4 import BLOCK as MX_BLOCK, E2M1_VALUES, _quantize_rows
 
 # keys per workgroup of the split kernel (csrc/attn_decode.hip takes it per launch; the
 # alternatives measured are in docs/PERFORMANCE.md)
@@ -202,7 +227,12 @@ GQA_CHUNK_STEP = 128
 CHUNK_PREFILL_GQA = 512
 # query heads per KV head that the grouped-query HIP kernels serve
 GQA_GROUPS = (2, 4, 8, 16)
-KV_DTYPES = ("bf16", "fp8")
+# keys per workgroup of the MXFP4-cache split kernel (csrc/attn_decode.hip, attn_decode_mxfp4_kernel),
+# a constant of its own by CHUNK_FP8's rule: one value, no dispatch. 256 / 512 / 1024 measured
+# (docs/PERFORMANCE.md, "Decode: MXFP4 KV cache"): 512 is within 20 % of the best of the three on
+# every row; 256 is up to 56 % off (the rows of >= 256 MiB of bf16 K + V), 1024 up to 30 %
+CHUNK_MXFP4 = 512
+KV_DTYPES = ("bf16", "fp8", "mxfp4")
 # page sizes of the paged cache (positions per page; csrc/attn_decode.hip checks the same set)
 PAGE_SIZES = (16, 32, 64, 128, 256)
 # default page size of the paged cache. 16 / 64 / 256 measured against the contiguous per-sequence
@@ -295,8 +325,10 @@ class KVCache:
     """K / V of every layer of one rank, the shared device ``length``, and the split kernel's
     workspace. ``num_layers = 0`` holds no K / V (the stateless ``attention="slice"`` stub):
     only the position bookkeeping. ``kv_dtype="fp8"``: ``k`` / ``v`` hold e4m3 codes and
-    ``k_scale`` / ``v_scale`` one fp32 scale per cached row (module docstring); with ``"bf16"``
-    the two scale lists hold ``None`` per layer.
+    ``k_scale`` / ``v_scale`` one fp32 scale per cached row (module docstring); ``"mxfp4"``: ``k`` /
+    ``v`` hold ``uint8 [B, H, L_max, D/2]`` e2m1 pairs and the scales ``uint8 [B, H, L_max, D/32]``
+    e8m0 bytes (initially 127), contiguous caches only; with ``"bf16"`` the two scale lists hold
+    ``None`` per layer.
 
     ``per_sequence=True``: ``length`` is ``int32[B]`` and ``pos`` a list of ``B`` host mirrors, one
     per batch row; a negative entry is an empty slot (module docstring). :meth:`set_lengths`,
@@ -335,6 +367,13 @@ class KVCache:
                              f"{n_head_local} KV heads")
         if gqa and (kv_dtype != "bf16" or page_size is not None):
             raise ValueError("KVCache: paged and FP8 grouped-query (GQA) caches are not built yet")
+        mx4 = kv_dtype == "mxfp4"
+        if mx4 and (page_size is not None or n_pages is not None):
+            raise ValueError("KVCache: a paged MXFP4 cache is not built (page_size= goes with "
+                             "kv_dtype 'bf16' or 'fp8')")
+        if mx4 and int(head_dim) % MX_BLOCK:
+            raise ValueError(f"KVCache kv_dtype 'mxfp4' needs head_dim % {MX_BLOCK} == 0, got "
+                             f"{head_dim}")
         self.per_sequence = bool(per_sequence) or page_size is not None
         self.page_size: Optional[int] = None
         self._pages: Optional[_PageAllocator] = None
@@ -358,10 +397,13 @@ class KVCache:
         fp8 = kv_dtype == "fp8"
         if fp8:
             dtype = E4M3
+        if mx4:
+            dtype = torch.uint8
         self.num_layers, self.batch = int(num_layers), int(batch)
         self.n_head, self.head_dim, self.max_len = int(n_head_local), int(head_dim), int(max_len)
         self.device = torch.device(device)
-        shape = (self.batch, self.n_head, self.max_len, self.head_dim)
+        shape = (self.batch, self.n_head, self.max_len,
+                 self.head_dim // 2 if mx4 else self.head_dim)
         if self.page_size is not None:
             shape = (n_pages, self.n_head, self.page_size, self.head_dim)
             self._pages = _PageAllocator(n_pages, self.page_size, self.batch, max_pages,
@@ -370,12 +412,16 @@ class KVCache:
                                       for _ in range(self.num_layers)]
         self.v: List[torch.Tensor] = [torch.zeros(shape, dtype=dtype, device=self.device)
                                       for _ in range(self.num_layers)]
-        self.k_scale: List[Optional[torch.Tensor]] = [
-            torch.ones(shape[:3], dtype=torch.float32, device=self.device) if fp8 else None
-            for _ in range(self.num_layers)]
-        self.v_scale: List[Optional[torch.Tensor]] = [
-            torch.ones(shape[:3], dtype=torch.float32, device=self.device) if fp8 else None
-            for _ in range(self.num_layers)]
+        def scales() -> Optional[torch.Tensor]:
+            if fp8:
+                return torch.ones(shape[:3], dtype=torch.float32, device=self.device)
+            if mx4:                             # e8m0 127 = 2^0
+                return torch.full(shape[:3] + (self.head_dim // MX_BLOCK,), 127,
+                                  dtype=torch.uint8, device=self.device)
+            return None
+
+        self.k_scale: List[Optional[torch.Tensor]] = [scales() for _ in range(self.num_layers)]
+        self.v_scale: List[Optional[torch.Tensor]] = [scales() for _ in range(self.num_layers)]
         self.length = torch.zeros(self.batch if self.per_sequence else 1, dtype=torch.int32,
                                   device=self.device)
         # host mirror of `length`: bounds checks only (a list of B with per_sequence)
@@ -385,7 +431,8 @@ class KVCache:
         self.len_bound: Optional[int] = None
         self.workspace = (torch.empty(workspace_numel(self.batch, self.n_q_head, self.head_dim,
                                                       self.max_len, CHUNK_GQA if gqa else
-                                                      CHUNK_FP8 if fp8 else CHUNK),
+                                                      CHUNK_FP8 if fp8 else
+                                                      CHUNK_MXFP4 if mx4 else CHUNK),
                                       dtype=torch.float32, device=self.device)
                           if self.num_layers else None)
 
@@ -571,7 +618,9 @@ class KVCache:
 
     def _position_bytes(self) -> int:
         """K, V and scale bytes of one cached position of one batch row, over every layer."""
-        row = self.head_dim + 4 if self.kv_dtype == "fp8" else 2 * self.head_dim
+        row = {"fp8": self.head_dim + 4,
+               "mxfp4": self.head_dim // 2 + self.head_dim // MX_BLOCK}.get(self.kv_dtype,
+                                                                            2 * self.head_dim)
         return self.num_layers * self.n_head * row * 2
 
     def live_bytes(self) -> int:
@@ -583,7 +632,7 @@ class KVCache:
 
     @property
     def nbytes(self) -> int:
-        """Bytes of K and V over every layer (codes and scales for the FP8 cache)."""
+        """Bytes of K and V over every layer (codes and scales for the FP8 and MXFP4 caches)."""
         return sum(t.numel() * t.element_size()
                    for t in self.k + self.v + self.k_scale + self.v_scale if t is not None)
 
@@ -597,6 +646,13 @@ def hip_supported(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     if qkv.shape[2] % 3 or C % n_head or C // n_head not in HEAD_DIMS:
         return False
     shape = (qkv.shape[0], n_head, k_cache.shape[2] if k_cache.dim() == 4 else -1, C // n_head)
+    if k_scale is not None and k_scale.dtype == torch.uint8:    # the MXFP4 cache
+        D = shape[3]
+        return (all(t.dtype == torch.uint8 and t.is_contiguous()
+                    and tuple(t.shape) == shape[:3] + (D // 2,) for t in (k_cache, v_cache))
+                and all(t is not None and t.dtype == torch.uint8 and t.is_contiguous()
+                        and tuple(t.shape) == shape[:3] + (D // MX_BLOCK,)
+                        for t in (k_scale, v_scale)))
     if k_scale is not None or v_scale is not None:
         return (all(t.dtype == E4M3 and t.is_contiguous() and tuple(t.shape) == shape
                     for t in (k_cache, v_cache))
@@ -625,6 +681,31 @@ def _check_fp8_cache(k_cache, v_cache, k_scale, v_scale) -> bool:
             or tuple(k_scale.shape) != tuple(k_cache.shape[:3]) \
             or tuple(v_scale.shape) != tuple(v_cache.shape[:3]):
         raise ValueError("k_scale / v_scale must be fp32 [B, H, L_max]")
+    return True
+
+
+def _check_mxfp4_cache(what: str, k_cache, v_cache, k_scale, v_scale) -> bool:
+    """True for the MXFP4 cache: ``uint8`` caches ``[B, H, L_max, D/2]`` with ``uint8`` scales
+    ``[B, H, L_max, D/32]``; False when neither scale is ``uint8`` (the bf16 / FP8 checks follow);
+    raises ``ValueError`` naming what is wrong with a half-formed one."""
+    if not any(t is not None and t.dtype == torch.uint8 for t in (k_scale, v_scale)):
+        if k_scale is None and v_scale is None and torch.uint8 in (k_cache.dtype, v_cache.dtype):
+            raise ValueError(f"{what}: a uint8 (MXFP4) KV cache needs its uint8 k_scale / v_scale")
+        return False
+    if k_scale is None or v_scale is None or k_scale.dtype != v_scale.dtype:
+        raise ValueError(f"{what}: uint8 (e8m0) k_scale and v_scale go together")
+    if k_cache.dtype != torch.uint8 or v_cache.dtype != torch.uint8:
+        raise ValueError(f"{what}: uint8 (e8m0) scales go with uint8 MXFP4 caches, got "
+                         f"{k_cache.dtype} / {v_cache.dtype}")
+    for name, c, sc in (("k", k_cache, k_scale), ("v", v_cache, v_scale)):
+        D = 2 * c.shape[-1]
+        if c.dim() != 4 or D % MX_BLOCK or tuple(sc.shape) != tuple(c.shape[:3]) + (D // MX_BLOCK,):
+            raise ValueError(f"{what}: MXFP4 {name}_cache {tuple(c.shape)} is [B, H, L_max, D/2] "
+                             f"with D % {MX_BLOCK} == 0 and {name}_scale [B, H, L_max, "
+                             f"D/{MX_BLOCK}], got scales {tuple(sc.shape)}")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"{what}: MXFP4 k_cache {tuple(k_cache.shape)} vs v_cache "
+                         f"{tuple(v_cache.shape)}")
     return True
 
 
@@ -677,6 +758,13 @@ def torch_kv_append(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
         k_cache[:, :, pos:pos + T] = k
         v_cache[:, :, pos:pos + T] = v
         return
+    if k_scale.dtype == torch.uint8:            # MXFP4: codes [.., D/2] and e8m0 bytes [.., D/32]
+        for rows, cache, scale in ((k, k_cache, k_scale), (v, v_cache, v_scale)):
+            B, H, _, D = rows.shape
+            code, s = _quantize_rows(rows.float().reshape(-1, D))
+            cache[:, :, pos:pos + T] = code.view(B, H, T, D // 2)
+            scale[:, :, pos:pos + T] = s.view(B, H, T, D // MX_BLOCK)
+        return
     for rows, cache, scale in ((k, k_cache, k_scale), (v, v_cache, v_scale)):
         code, s = _quantize_torch(rows)
         cache.view(torch.uint8)[:, :, pos:pos + T] = code.view(torch.uint8)
@@ -684,7 +772,16 @@ def torch_kv_append(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
 
 
 def dequantize(cache: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
-    """fp32 rows of an FP8 cache (or a slice of one): ``float(code) * scale``."""
+    """fp32 rows of an FP8 cache (or a slice of one): ``float(code) * scale``; of an MXFP4 cache
+    (``uint8`` codes ``[..., D/2]`` and e8m0 bytes ``[..., D/32]``): the rule of
+    ``mxfp4.dequantize_mxfp4``, exactly."""
+    if scale.dtype == torch.uint8:
+        lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32,
+                           device=cache.device)
+        nib = torch.stack((cache & 15, cache >> 4), dim=-1)      # [..., D/2, 2]: element order
+        v = lut[nib.long()].reshape(*scale.shape, MX_BLOCK)
+        return torch.ldexp(v, (scale.to(torch.int32) - 127).unsqueeze(-1)).reshape(
+            *cache.shape[:-1], 2 * cache.shape[-1])
     return cache.float() * scale[..., None]
 
 
@@ -769,12 +866,14 @@ def torch_decode_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence
 
 
 def _hip_append(qkv, n_head: int, k_cache, v_cache, k_scale, v_scale, length, T: int) -> None:
-    """The HIP append of ``T`` tokens; the FP8 entry point when the cache has scales, the
+    """The HIP append of ``T`` tokens; the FP8 entry point when the cache has scales (the MXFP4
+    one when they are ``uint8``), the
     ``_seq`` one when ``length`` has an element per batch row."""
     B, _, C3 = qkv.shape
     fp8 = k_scale is not None
     scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
-    name = ("dlbb_kv_append_fp8" if fp8 else "dlbb_kv_append") + \
+    name = "dlbb_kv_append" + ("" if not fp8 else
+                               "_mxfp4" if k_scale.dtype == torch.uint8 else "_fp8") + \
         ("_seq" if length.numel() != 1 else "")
     fn = getattr(_lib.lib(), name)
     check(fn(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(), *scales,
@@ -791,7 +890,8 @@ def _hip_decode(qkv, n_head: int, k_cache, v_cache, k_scale, v_scale, length, wo
     D = C // n_head
     fp8 = k_scale is not None
     scales = (k_scale.data_ptr(), v_scale.data_ptr()) if fp8 else ()
-    name = ("dlbb_attn_decode_fp8" if fp8 else "dlbb_attn_decode") + \
+    name = "dlbb_attn_decode" + ("" if not fp8 else
+                                 "_mxfp4" if k_scale.dtype == torch.uint8 else "_fp8") + \
         ("_seq" if length.numel() != 1 else "")
     fn = getattr(_lib.lib(), name)
     check(fn(qkv.data_ptr(), C3, k_cache.data_ptr(), v_cache.data_ptr(), *scales,
@@ -870,6 +970,13 @@ class _Paged:
         return (self.table.data_ptr(), self.table.stride(0), self.n_pages, self.P)
 
 
+def _no_mxfp4(what: str, form: str, k_cache, v_cache, k_scale, v_scale) -> None:
+    """``ValueError`` when the call carries an MXFP4 cache (``uint8`` caches or scales)."""
+    if any(t is not None and t.dtype == torch.uint8 for t in (k_cache, v_cache, k_scale, v_scale)):
+        raise ValueError(f"{what}: {form} is not built (MXFP4 serves kv_append and "
+                         "decode_attention on contiguous, ungrouped caches)")
+
+
 def _gather_pages(pool: torch.Tensor, pages: Sequence[int]) -> torch.Tensor:
     """``pool[pages]`` as one contiguous batch-1 cache ``[1, H, len(pages) * P, ...]``."""
     raw = pool.view(torch.uint8) if pool.dtype == E4M3 else pool
@@ -944,6 +1051,7 @@ def torch_decode_attention_paged(qkv, n_head: int, k_pool, v_pool, table: Sequen
 def _kv_append_paged(qkv, n_head, k_pool, v_pool, length, pos, k_scale, v_scale, block_table,
                      table_host, max_len, n_keep) -> None:
     """:func:`kv_append` with a block table (module docstring, "Paged cache")."""
+    _no_mxfp4("kv_append", "a paged MXFP4 cache", k_pool, v_pool, k_scale, v_scale)
     g = _Paged("kv_append", qkv, k_pool, v_pool, length, block_table, table_host, max_len)
     T = qkv.shape[1]
     _check_fp8_cache(k_pool, v_pool, k_scale, v_scale)
@@ -975,6 +1083,7 @@ def _kv_append_paged(qkv, n_head, k_pool, v_pool, length, pos, k_scale, v_scale,
 def _decode_attention_paged(qkv, n_head, k_pool, v_pool, length, len_bound, workspace, pos, chunk,
                             fused, k_scale, v_scale, block_table, table_host, max_len):
     """:func:`decode_attention` with a block table (module docstring, "Paged cache")."""
+    _no_mxfp4("decode_attention", "a paged MXFP4 cache", k_pool, v_pool, k_scale, v_scale)
     g = _Paged("decode_attention", qkv, k_pool, v_pool, length, block_table, table_host, max_len)
     L_max = g.L_max
     fp8 = _check_fp8_cache(k_pool, v_pool, k_scale, v_scale)
@@ -1177,6 +1286,8 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
         _gqa_check("prefill_attention", k_cache, v_cache, k_scale, v_scale, block_table)
         return _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos,
                                       key_split, len_bound, workspace, window)
+    _no_mxfp4("prefill_attention", "prefill over an MXFP4 cache", k_cache, v_cache, k_scale,
+              v_scale)
     fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     B, T, C3 = qkv.shape
     C = C3 // 3
@@ -1226,6 +1337,7 @@ def _gqa_check(what: str, k_cache, v_cache, k_scale, v_scale, block_table) -> No
         raise ValueError(f"{what}: paged grouped-query (GQA) caches are not built yet")
     if k_scale is not None or v_scale is not None or E4M3 in (k_cache.dtype, v_cache.dtype):
         raise ValueError(f"{what}: FP8 grouped-query (GQA) caches are not built yet")
+    _no_mxfp4(what, "a grouped-query (GQA) MXFP4 cache", k_cache, v_cache, None, None)
 
 
 def _gqa_hip(what: str, qkv, n_head: int, n_kv_head: int, k_cache, v_cache) -> bool:
@@ -1407,7 +1519,8 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
     """K / V rows of ``qkv [B, T, 3C]`` -> cache positions ``[length, length + T)``. ``pos``:
     the host's copy of ``length`` (raises before launch on overflow; None on the HIP path = no
     host check, the kernel drops positions past the cache). ``k_scale`` / ``v_scale``: the row
-    scales of an FP8 cache (module docstring), whose rows are quantised on the way in. A
+    scales of an FP8 cache, or the ``uint8`` e8m0 block scales of an MXFP4 cache (module
+    docstring), whose rows are quantised on the way in. A
     ``length`` of ``B`` elements is the per-sequence form (module docstring): row ``b`` goes to
     ``[length[b], length[b] + T)``, ``pos`` is then a sequence of ``B`` host positions.
 
@@ -1434,7 +1547,8 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
             if max(pos) + T > L_max:
                 raise ValueError(f"kv_append: position {max(pos)} + {T} tokens > cache length "
                                  f"{L_max}")
-        _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+        if not _check_mxfp4_cache("kv_append", k_cache, v_cache, k_scale, v_scale):
+            _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
         if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale):
             _hip_append(qkv, n_head, k_cache, v_cache, k_scale, v_scale, length, T)
             return
@@ -1445,7 +1559,8 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
         return
     if pos is not None and pos + T > L_max:
         raise ValueError(f"kv_append: position {pos} + {T} tokens > cache length {L_max}")
-    _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+    if not _check_mxfp4_cache("kv_append", k_cache, v_cache, k_scale, v_scale):
+        _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale):
         _hip_append(qkv, n_head, k_cache, v_cache, k_scale, v_scale, length, T)
         return
@@ -1476,7 +1591,10 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     ``length`` for the overflow check (and the torch path). ``chunk`` / ``fused``: A/B knobs of
     ``tools/decode_bench.py`` (defaults :data:`CHUNK`, :data:`FUSED_APPEND`). ``k_scale`` /
     ``v_scale``: the row scales of an FP8 cache (module docstring): the token is stored
-    quantised and attended to in that form; the chunk default is then :data:`CHUNK_FP8`.
+    quantised and attended to in that form; the chunk default is then :data:`CHUNK_FP8`. ``uint8``
+    scales ``[B, H, L_max, D/32]`` with ``uint8`` caches ``[B, H, L_max, D/2]`` are the MXFP4 cache
+    (module docstring), under the same rule with :data:`CHUNK_MXFP4`; contiguous, ungrouped
+    caches only (``ValueError`` with a ``block_table`` or ``n_kv_head``).
 
     A ``length`` of ``B`` elements is the per-sequence form (module docstring): row ``b`` attends
     over ``length[b] + 1`` keys, an empty slot (``length[b] < 0``) gives a zero row; ``len_bound``
@@ -1518,12 +1636,13 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
         pos = max(host)                          # the longest row: what the checks below bound
     if pos is not None and pos + 1 > L_max:
         raise ValueError(f"decode_attention: position {pos} + 1 > cache length {L_max}")
-    fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+    mx4 = _check_mxfp4_cache("decode_attention", k_cache, v_cache, k_scale, v_scale)
+    fp8 = not mx4 and _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     if use_hip(qkv) and hip_supported(qkv, n_head, k_cache, v_cache, k_scale, v_scale):
         B, _, C3 = qkv.shape
         C = C3 // 3
         D = C // n_head
-        chunk = int(chunk or (CHUNK_FP8 if fp8 else CHUNK))
+        chunk = int(chunk or (CHUNK_MXFP4 if mx4 else CHUNK_FP8 if fp8 else CHUNK))
         fused = FUSED_APPEND if fused is None else bool(fused)
         bound = L_max if len_bound is None else max(1, min(int(len_bound), L_max))
         if pos is not None and pos + 1 > bound:

@@ -38,6 +38,9 @@ Additions (all optional, defaults keep reference behaviour):
   holds e4m3 codes with one fp32 scale per cached row of ``head_dim`` values (``ops.decode``;
   ``run_tp --kv-cache``): ``head_dim + 4`` bytes per row instead of ``2 head_dim``. The appends
   quantise, a decode step attends to the quantised rows; the prefill attention is unchanged.
+  ``mxfp4``: e2m1 codes with one e8m0 scale per 32 columns of a cached row, ``head_dim / 2 +
+  head_dim / 32`` bytes per row, under the same rules; not with ``kv_page_size`` or
+  ``prefill_chunk``.
 * ``execution.prompt_lengths``: absent (default: every prompt fills ``sequence_length``) | a list
   of ``batch_size`` ints in ``[1, sequence_length]`` — the batch is right-padded prompts of these
   lengths and the decode steps run over a per-sequence KV cache (``ops.decode``;
@@ -165,8 +168,8 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
         check_w8_shapes(cfg, ws if isinstance(ws, int) else 1)
     if ex["decode_weight_dtype"] == "mxfp4":
         check_w4_shapes(cfg, ws if isinstance(ws, int) else 1)
-    if ex["kv_cache_dtype"] not in ("bf16", "fp8"):
-        raise ConfigError("execution.kv_cache_dtype must be bf16|fp8, got "
+    if ex["kv_cache_dtype"] not in ("bf16", "fp8", "mxfp4"):
+        raise ConfigError("execution.kv_cache_dtype must be bf16|fp8|mxfp4, got "
                           f"{ex['kv_cache_dtype']!r}")
     lens = ex.get("prompt_lengths")             # no default: absent = every prompt is full
     if lens is not None:
@@ -188,6 +191,9 @@ def validate_config(config: Dict[str, Any]) -> Dict[str, Any]:
             raise ConfigError(f"execution.kv_pool_pages must be an int >= 1, got {pool!r}")
         if page is None:
             raise ConfigError("execution.kv_pool_pages needs execution.kv_page_size")
+    if page is not None and ex["kv_cache_dtype"] == "mxfp4":
+        raise ConfigError("execution.kv_page_size needs kv_cache_dtype bf16|fp8: a paged MXFP4 "
+                          "cache is not built")
     chunk = ex.get("prefill_chunk")             # no default: absent = one-shot prefill
     if chunk is not None:
         if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:

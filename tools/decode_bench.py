@@ -18,6 +18,11 @@ kv_append + attention form of the same step. Rows go to ``profiles/decode/attn_d
 the decode step over caches holding the same K / V as e4m3 codes + one fp32 scale per row
 (``D + 4`` bytes per row; rotated over as many caches as the bf16 form), ``copy_fp8`` a device copy
 of exactly those code + scale bytes, ``ours_fp8_chunk<N>`` the kernel at the other ``--fp8-chunks``.
+``--mxfp4`` adds the MXFP4 (e2m1 + e8m0) KV cache the same way (uniform rows only): ``ours_mxfp4``
+on the same K / V quantised per 32-column block (``D / 2 + D / 32`` bytes per row), ``copy_mxfp4`` a
+device copy of exactly those code + scale bytes, ``ours_mxfp4_chunk<N>`` the other
+``--mxfp4-chunks``; ``mxfp4_over_bf16`` / ``mxfp4_over_fp8`` are time ratios,
+``mxfp4_vs_bf16_max_rel_diff`` the output distance to the bf16-cache kernel.
 ``GBps`` of these candidates is over the bytes they actually read (``kv_bytes_fp8``);
 ``fp8_over_bf16`` is ``us[ours_fp8] / us[ours]``, ``fp8_vs_bf16_max_rel_diff`` the output distance
 of the two cache types on the row's inputs.
@@ -140,6 +145,35 @@ def bench_row(B, H, D, L, args):
             if c != dec.CHUNK_FP8:
                 cands[f"ours_fp8_chunk{c}"] = lambda i, c=c: ours_fp8(i, chunk=c)
 
+    kv_bytes_mx4 = 2 * B * H * L * (D // 2 + D // 32)
+    if args.mxfp4:
+        from distributed_llm_backend_benchmark_amd.ops import mxfp4
+
+        # the same K / V as MXFP4: codes [2, B, H, L, D / 2] and e8m0 bytes [2, B, H, L, D / 32]
+        caches4 = []
+        for kv in caches:
+            q4, s4 = mxfp4.quantize_rows_mxfp4(kv.reshape(-1, D))
+            caches4.append((q4.view(2, B, H, L, D // 2), s4.view(2, B, H, L, D // 32)))
+        sink4 = (torch.empty_like(caches4[0][0]), torch.empty_like(caches4[0][1]))
+        chunks4 = sorted(set(args.mxfp4_chunks))
+        ws4 = torch.empty(dec.workspace_numel(B, H, D, L, min(chunks4 + [dec.CHUNK_MXFP4])),
+                          dtype=torch.float32, device=dev)
+
+        def ours_mxfp4(i, **kw):
+            (kc, vc), (ks, vs) = caches4[i % nbuf]
+            return dec.decode_attention(qkv, H, kc, vc, length, workspace=ws4, k_scale=ks,
+                                        v_scale=vs, **kw)
+
+        def copy_mxfp4(i):
+            sink4[0].copy_(caches4[i % nbuf][0])
+            sink4[1].copy_(caches4[i % nbuf][1])
+
+        cands["ours_mxfp4"] = ours_mxfp4
+        cands["copy_mxfp4"] = copy_mxfp4
+        for c in chunks4:
+            if c != dec.CHUNK_MXFP4:
+                cands[f"ours_mxfp4_chunk{c}"] = lambda i, c=c: ours_mxfp4(i, chunk=c)
+
     graphs = {}
     for name, fn in cands.items():                       # warm every candidate, then capture
         for i in range(nbuf + 1):
@@ -171,7 +205,8 @@ def bench_row(B, H, D, L, args):
            "rounds": args.rounds, "us": us,
            "us_min": {n: min(v) for n, v in times.items()},
            "GBps": {n: (2 if n.startswith("copy") else 1)
-                    * (kv_bytes_fp8 if "fp8" in n else kv_bytes) / (t * 1e-6) / 1e9
+                    * (kv_bytes_fp8 if "fp8" in n else kv_bytes_mx4 if "mxfp4" in n else kv_bytes)
+                    / (t * 1e-6) / 1e9
                     for n, t in us.items()},
            "max_rel_diff_vs_sdpa": err}
     row["share_of_copy"] = row["GBps"]["ours"] / row["GBps"]["copy"]
@@ -183,6 +218,15 @@ def bench_row(B, H, D, L, args):
         row["fp8_over_bf16"] = us["ours_fp8"] / us["ours"]
         row["fp8_vs_bf16_max_rel_diff"] = float((ours_fp8(0).float() - ours(0).float()).abs().max()
                                                 / ref.abs().max())
+    if args.mxfp4:
+        row["kv_bytes_mxfp4"] = kv_bytes_mx4
+        row["chunk_mxfp4"] = dec.CHUNK_MXFP4
+        row["share_of_copy_mxfp4"] = row["GBps"]["ours_mxfp4"] / row["GBps"]["copy_mxfp4"]
+        row["mxfp4_over_bf16"] = us["ours_mxfp4"] / us["ours"]
+        if args.fp8:
+            row["mxfp4_over_fp8"] = us["ours_mxfp4"] / us["ours_fp8"]
+        row["mxfp4_vs_bf16_max_rel_diff"] = float(
+            (ours_mxfp4(0).float() - ours(0).float()).abs().max() / ref.abs().max())
     return row
 
 
@@ -609,6 +653,10 @@ def main(argv=None) -> int:
     ap.add_argument("--fp8", action="store_true",
                     help="also time the FP8 (e4m3) KV cache: ours_fp8, copy_fp8, --fp8-chunks")
     ap.add_argument("--fp8-chunks", type=int, nargs="*", default=[256, 512, 1024])
+    ap.add_argument("--mxfp4", action="store_true",
+                    help="also time the MXFP4 (e2m1 + e8m0) KV cache on the uniform rows: "
+                         "ours_mxfp4, copy_mxfp4, --mxfp4-chunks")
+    ap.add_argument("--mxfp4-chunks", type=int, nargs="*", default=[256, 512, 1024])
     ap.add_argument("--ragged", action="store_true",
                     help="time the per-sequence kernels on a batch of spread lengths instead: "
                          "ragged, uniform, uniform_seq, copy_live, copy (with --fp8 also *_fp8)")
@@ -692,7 +740,9 @@ def main(argv=None) -> int:
                   + f"  share_of_copy {row['share_of_copy']:.2f}  ours/sdpa "
                   f"{row['ours_over_sdpa']:.2f}" +
                   (f"  fp8/bf16 {row['fp8_over_bf16']:.2f}  share_of_copy_fp8 "
-                   f"{row['share_of_copy_fp8']:.2f}" if args.fp8 else ""), flush=True)
+                   f"{row['share_of_copy_fp8']:.2f}" if args.fp8 else "") +
+                  (f"  mxfp4/bf16 {row['mxfp4_over_bf16']:.2f}  share_of_copy_mxfp4 "
+                   f"{row['share_of_copy_mxfp4']:.2f}" if args.mxfp4 else ""), flush=True)
     return 0
 
 
