@@ -67,6 +67,16 @@
 // alignment). With W >= L the result has the bits of the unwindowed launch at the same chunk;
 // when the window bites, those of an unwindowed launch on a cache holding keys [lo, L) at
 // positions 0 .. L - lo - 1.
+//
+// Rotary position embedding (the Rope instantiations, dlbb_*_gqa*_rope*; the table and the rotation
+// are attn_tile.h's rope_rotate8). K is rotated ONCE, on its way into the cache, at its own cache
+// position; V is stored untouched. Q is rotated in registers right after the split kernel's loads:
+// the lane that holds Q[head][32 ks + 8 g + j] holds the partner column 32 (ks + D / 64) + 8 g + j
+// too, so the rotation needs no other lane, no LDS and no launch of its own. The table row is
+// L - 1, the ABSOLUTE cache position of the decoded token (under a window too, where the keys are
+// addressed from lo); every chunk's workgroup rotates its copy of Q at that same row, and the
+// padding columns rotate head G - 1 (finite). Nothing in the key loop differs and the combine
+// kernel is the unroped one. The table must have at least L_max rows (the caller's check).
 #include "attn_tile.h"
 #include "common.h"
 
@@ -86,6 +96,7 @@ struct GqaAppendArgs {
   const int* length;
   int64_t ld;
   int B, T, Hq, Hkv, D, L_max;
+  const float* rope;     // the Rope kernel: cos | sin rows [>= L_max, D] fp32
 };
 
 // one 16-byte vector per thread step: (b, t, k|v, h_kv, piece). PerSeq: length[b], not *length
@@ -118,6 +129,51 @@ __global__ __launch_bounds__(256) void kv_append_gqa_kernel(GqaAppendArgs a) {
   }
 }
 
+// The same with K rotated at its cache position (V is copied as above). A K work item is a PAIR:
+// the 16-byte piece `piece` of the row's low half and the matching piece of its high half, with
+// the 8 cos and 8 sin floats of the position: D / 16 K items and D / 8 V items per (b, t, h_kv).
+// The guards come first: an empty slot or a position past the cache reads no K, V or table row
+template <bool PerSeq>
+__global__ __launch_bounds__(256) void kv_append_gqa_rope_kernel(GqaAppendArgs a) {
+  [[maybe_unused]] const int len0 = PerSeq ? 0 : *a.length;
+  const int vpr = a.D / 8, kpr = a.D / 16;                  // V / K items per head row
+  const int kitems = a.Hkv * kpr;
+  const int64_t per_tok = kitems + static_cast<int64_t>(a.Hkv) * vpr;
+  const int64_t total = static_cast<int64_t>(a.B) * a.T * per_tok;
+  const int64_t step = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+       i += step) {
+    const int64_t tok = i / per_tok;
+    const int r = static_cast<int>(i - tok * per_tok);      // K: (h, pair); then V: (h, piece)
+    const int b = static_cast<int>(tok / a.T), t = static_cast<int>(tok - (int64_t)b * a.T);
+    int len;
+    if constexpr (PerSeq) len = a.length[b];
+    else len = len0;
+    const int64_t pos = static_cast<int64_t>(len) + t;
+    if (len < 0 || pos >= a.L_max) continue;                // device-side guard: never past the cache
+    const uint16_t* src = a.qkv + (static_cast<int64_t>(b) * a.T + t) * a.ld +
+                          static_cast<int64_t>(a.Hq) * a.D;  // the token's K heads, then its V heads
+    if (r < kitems) {
+      const int h = r / kpr, piece = r - h * kpr;
+      const uint16_t* sp = src + h * a.D + piece * 8;
+      u16x8 lo = *reinterpret_cast<const u16x8*>(sp);
+      u16x8 hi = *reinterpret_cast<const u16x8*>(sp + a.D / 2);
+      rope_rotate8(lo, hi, a.rope + pos * a.D + piece * 8, a.D / 2);
+      uint16_t* dst = a.k_cache +
+                      ((static_cast<int64_t>(b) * a.Hkv + h) * a.L_max + pos) * a.D + piece * 8;
+      *reinterpret_cast<u16x8*>(dst) = lo;
+      *reinterpret_cast<u16x8*>(dst + a.D / 2) = hi;
+    } else {
+      const int hp = r - kitems;                            // h * vpr + piece
+      const int h = hp / vpr, piece = hp - h * vpr;
+      const u16x8 val = *reinterpret_cast<const u16x8*>(src + a.Hkv * a.D + hp * 8);
+      uint16_t* dst = a.v_cache +
+                      ((static_cast<int64_t>(b) * a.Hkv + h) * a.L_max + pos) * a.D + piece * 8;
+      *reinterpret_cast<u16x8*>(dst) = val;
+    }
+  }
+}
+
 struct GqaArgs {
   const uint16_t* qkv;      // [B, 1, H_q + 2 H_kv, D], batch row stride ld
   const uint16_t* k_cache;  // [B, H_kv, L_max, D]
@@ -129,6 +185,7 @@ struct GqaArgs {
   int B, Hq, Hkv, G, L_max, chunk, n_chunks;
   float scale_log2;         // log2(e) * scale
   int window;               // Win kernels: keys a query attends, 1 .. L_max
+  const float* rope;        // Rope kernels: cos | sin rows [>= L_max, D] fp32
 };
 
 // keys row b attends: positions 0 .. min(len, L_max - 1) (the token was appended at `len`).
@@ -155,7 +212,7 @@ __device__ __forceinline__ int gqa_window_lo(const GqaArgs& a, int L) {
   return L > a.window ? L - a.window : 0;
 }
 
-template <int D, bool PerSeq, bool Win>
+template <int D, bool PerSeq, bool Win, bool Rope>
 __global__ void __launch_bounds__(kGqaThreads, 2) attn_decode_gqa_split_kernel(GqaArgs a) {
   constexpr int ROW = 2 * D;                 // bytes of a V row
   constexpr int RPI = 1024 / ROW;            // rows per DMA wave-instruction
@@ -191,6 +248,13 @@ __global__ void __launch_bounds__(kGqaThreads, 2) attn_decode_gqa_split_kernel(G
     const uint16_t* qp = a.qkv + static_cast<int64_t>(b) * a.ld + static_cast<int64_t>(hq) * D + 8 * g;
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 32 * ks);
+  }
+  // Rope: k-step ks holds the low-half columns 32 ks + 8 g + j, k-step ks + NKS / 2 their partners;
+  // table row L - 1 is the token's absolute position (not L - 1 - lo), < L_max
+  if constexpr (Rope) {
+    const float* cs = a.rope + static_cast<int64_t>(L - 1) * D + 8 * g;
+#pragma unroll
+    for (int ks = 0; ks < NKS / 2; ++ks) rope_rotate8(qf[ks], qf[ks + NKS / 2], cs + 32 * ks, D / 2);
   }
   const int64_t rows = (static_cast<int64_t>(b) * a.Hkv + kvh) * a.L_max;
   const uint16_t* kc = a.k_cache + rows * D + 8 * g;   // the lane's 8 columns of row 0
@@ -411,30 +475,40 @@ bool gqa_qkv_cache_ok(const void* qkv, int64_t ld, const void* k_cache, const vo
   return !(mis(qkv, 16) || mis(k_cache, 16) || mis(v_cache, 16));
 }
 
-template <bool PerSeq>
+// Rope: `rope` is the cos | sin table (fp32 [>= L_max, D], 16-byte aligned), K is stored rotated
+template <bool PerSeq, bool Rope = false>
 int gqa_append_launch(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
                       const void* length, int B, int T, int Hq, int Hkv, int D, int L_max,
-                      hipStream_t stream) {
+                      hipStream_t stream, const void* rope = nullptr) {
   if (!gqa_range_ok(Hq, Hkv, D)) return hipErrorInvalidValue;
+  if (Rope && (!rope || mis(rope, 16))) return hipErrorInvalidValue;
   if (B <= 0 || T <= 0) return hipSuccess;
   if (!gqa_qkv_cache_ok(qkv, ld, k_cache, v_cache, length, Hq, Hkv, D, L_max))
     return hipErrorInvalidValue;
   GqaAppendArgs a{static_cast<const uint16_t*>(qkv), static_cast<uint16_t*>(k_cache),
                   static_cast<uint16_t*>(v_cache), static_cast<const int*>(length), ld, B, T, Hq,
-                  Hkv, D, L_max};
-  const int64_t vecs = static_cast<int64_t>(B) * T * 2 * Hkv * (D / 8);
-  hipLaunchKernelGGL((kv_append_gqa_kernel<PerSeq>), dim3(stream_grid(vecs, 256)), dim3(256), 0,
-                     stream, a);
+                  Hkv, D, L_max, static_cast<const float*>(rope)};
+  if constexpr (Rope) {
+    const int64_t items = static_cast<int64_t>(B) * T * Hkv * (D / 16 + D / 8);
+    hipLaunchKernelGGL((kv_append_gqa_rope_kernel<PerSeq>), dim3(stream_grid(items, 256)),
+                       dim3(256), 0, stream, a);
+  } else {
+    const int64_t vecs = static_cast<int64_t>(B) * T * 2 * Hkv * (D / 8);
+    hipLaunchKernelGGL((kv_append_gqa_kernel<PerSeq>), dim3(stream_grid(vecs, 256)), dim3(256), 0,
+                       stream, a);
+  }
   return hipGetLastError();
 }
 
-// Win: `window` keys per query (>= 1, clamped to L_max: a window at or over L_max is no window)
-template <bool PerSeq, bool Win = false>
+// Win: `window` keys per query (>= 1, clamped to L_max: a window at or over L_max is no window).
+// Rope: `rope` is the cos | sin table (fp32 [>= L_max, D], 16-byte aligned), Q is rotated at L - 1
+template <bool PerSeq, bool Win = false, bool Rope = false>
 int gqa_decode_launch(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache,
                       const void* length, void* ws, void* out, int64_t ldo, int B, int Hq,
                       int Hkv, int D, int L_max, int len_bound, int chunk, float scale,
-                      hipStream_t stream, int window = 0) {
+                      hipStream_t stream, int window = 0, const void* rope = nullptr) {
   if (!gqa_range_ok(Hq, Hkv, D)) return hipErrorInvalidValue;
+  if (Rope && (!rope || mis(rope, 16))) return hipErrorInvalidValue;
   if (B <= 0) return hipSuccess;
   if (!gqa_qkv_cache_ok(qkv, ld, k_cache, v_cache, length, Hq, Hkv, D, L_max))
     return hipErrorInvalidValue;
@@ -450,14 +524,15 @@ int gqa_decode_launch(const void* qkv, int64_t ld, const void* k_cache, const vo
   GqaArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(k_cache),
             static_cast<const uint16_t*>(v_cache), static_cast<const int*>(length),
             static_cast<float*>(ws), static_cast<uint16_t*>(out), ld, ldo, B, Hq, Hkv, Hq / Hkv,
-            L_max, chunk, n_chunks, scale * 1.4426950408889634f, window};
+            L_max, chunk, n_chunks, scale * 1.4426950408889634f, window,
+            static_cast<const float*>(rope)};
   const dim3 gs(n_chunks, Hkv, B), gc(Hq, B);
   if (D == 64) {
-    hipLaunchKernelGGL((attn_decode_gqa_split_kernel<64, PerSeq, Win>), gs, dim3(kGqaThreads), 0,
+    hipLaunchKernelGGL((attn_decode_gqa_split_kernel<64, PerSeq, Win, Rope>), gs, dim3(kGqaThreads), 0,
                        stream, a);
     hipLaunchKernelGGL((attn_decode_gqa_combine_kernel<64, PerSeq, Win>), gc, dim3(64), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((attn_decode_gqa_split_kernel<128, PerSeq, Win>), gs, dim3(kGqaThreads), 0,
+    hipLaunchKernelGGL((attn_decode_gqa_split_kernel<128, PerSeq, Win, Rope>), gs, dim3(kGqaThreads), 0,
                        stream, a);
     hipLaunchKernelGGL((attn_decode_gqa_combine_kernel<128, PerSeq, Win>), gc, dim3(128), 0, stream, a);
   }
@@ -541,4 +616,70 @@ DLBB_API int dlbb_attn_decode_gqa_win_seq(const void* qkv, int64_t ld, const voi
                                           float scale, hipStream_t stream) {
   return gqa_decode_launch<true, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B, Hq,
                                        Hkv, D, L_max, len_bound, chunk, scale, stream, window);
+}
+
+// The rotary forms (the file header, "Rotary position embedding"): the entry points above with
+// `rope`, the cos | sin table (fp32 [P >= L_max, D] contiguous, 16-byte aligned; row p: cos of
+// cache position p in [0, D / 2), sin in [D / 2, D)), after `length`. A null or misaligned table
+// returns hipErrorInvalidValue before any launch. dlbb_kv_append_gqa_rope* store each K row rotated
+// at its own position *length + t (length[b] + t) and the V rows untouched.
+DLBB_API int dlbb_kv_append_gqa_rope(const void* qkv, int64_t ld, void* k_cache, void* v_cache,
+                                     const void* length, const void* rope, int B, int T, int Hq,
+                                     int Hkv, int D, int L_max, hipStream_t stream) {
+  return gqa_append_launch<false, true>(qkv, ld, k_cache, v_cache, length, B, T, Hq, Hkv, D, L_max,
+                                        stream, rope);
+}
+
+DLBB_API int dlbb_kv_append_gqa_rope_seq(const void* qkv, int64_t ld, void* k_cache,
+                                         void* v_cache, const void* length, const void* rope,
+                                         int B, int T, int Hq, int Hkv, int D, int L_max,
+                                         hipStream_t stream) {
+  return gqa_append_launch<true, true>(qkv, ld, k_cache, v_cache, length, B, T, Hq, Hkv, D, L_max,
+                                       stream, rope);
+}
+
+// dlbb_attn_decode_gqa* with Q rotated at table row min(*length, L_max - 1), the position at which
+// dlbb_kv_append_gqa_rope* stored the token's K; the cache must hold keys rotated with this table.
+DLBB_API int dlbb_attn_decode_gqa_rope(const void* qkv, int64_t ld, const void* k_cache,
+                                       const void* v_cache, const void* length, const void* rope,
+                                       void* ws, void* out, int64_t ldo, int B, int Hq, int Hkv,
+                                       int D, int L_max, int len_bound, int chunk, float scale,
+                                       hipStream_t stream) {
+  return gqa_decode_launch<false, false, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B,
+                                               Hq, Hkv, D, L_max, len_bound, chunk, scale, stream,
+                                               0, rope);
+}
+
+DLBB_API int dlbb_attn_decode_gqa_rope_seq(const void* qkv, int64_t ld, const void* k_cache,
+                                           const void* v_cache, const void* length,
+                                           const void* rope, void* ws, void* out, int64_t ldo,
+                                           int B, int Hq, int Hkv, int D, int L_max, int len_bound,
+                                           int chunk, float scale, hipStream_t stream) {
+  return gqa_decode_launch<true, false, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B,
+                                              Hq, Hkv, D, L_max, len_bound, chunk, scale, stream,
+                                              0, rope);
+}
+
+// The windowed forms: the table row is still the token's absolute position, not its place in the
+// window.
+DLBB_API int dlbb_attn_decode_gqa_win_rope(const void* qkv, int64_t ld, const void* k_cache,
+                                           const void* v_cache, const void* length,
+                                           const void* rope, void* ws, void* out, int64_t ldo,
+                                           int B, int Hq, int Hkv, int D, int L_max, int len_bound,
+                                           int chunk, int window, float scale,
+                                           hipStream_t stream) {
+  return gqa_decode_launch<false, true, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B,
+                                              Hq, Hkv, D, L_max, len_bound, chunk, scale, stream,
+                                              window, rope);
+}
+
+DLBB_API int dlbb_attn_decode_gqa_win_rope_seq(const void* qkv, int64_t ld, const void* k_cache,
+                                               const void* v_cache, const void* length,
+                                               const void* rope, void* ws, void* out, int64_t ldo,
+                                               int B, int Hq, int Hkv, int D, int L_max,
+                                               int len_bound, int chunk, int window, float scale,
+                                               hipStream_t stream) {
+  return gqa_decode_launch<true, true, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B,
+                                             Hq, Hkv, D, L_max, len_bound, chunk, scale, stream,
+                                             window, rope);
 }

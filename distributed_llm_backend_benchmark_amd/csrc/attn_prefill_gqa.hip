@@ -58,6 +58,14 @@
 //     has a tile max of -1e30 below the half-start running max: the max does not move, alpha = 1,
 //     p = 0. A token past the cache with no visible key ends with l = 0 and writes zeros.
 //   * With W >= len_b + T every bound is 0 and the launch has the bits of the unwindowed kernel.
+// Rotary position embedding (the Rope instantiations, dlbb_attn_prefill_gqa*_rope*; the table and
+// the rotation are attn_tile.h's rope_rotate8): the lane that holds Q[tok][head][16 ks + 8 hi + j]
+// holds the partner column 16 (ks + D / 32) + 8 hi + j too, so Q is rotated in registers right
+// after the gather, at table row len_b + token(lane), the row at which dlbb_kv_append_gqa_rope*
+// stored that token's K. A lane whose token is at or past T takes the row of token T - 1 with its
+// values (inside the table, finite); a position at or past L_max takes row L_max - 1 (the table
+// has L_max rows; such a token has no key of its own in the cache). Nothing in the tile loop
+// differs.
 // Not here: a split of the keys across workgroups (a short block over a long prefix runs
 // H_kv B workgroups; under a window it visits the window's tiles only), paged and FP8 grouped
 // caches.
@@ -81,9 +89,10 @@ struct PrefillGqaArgs {
   int gsh;                  // log2 G
   float scale_log2;         // log2(e) * scale
   int window;               // Win kernels: keys a token attends, >= 1
+  const float* rope;        // Rope kernels: cos | sin rows [>= L_max, D] fp32
 };
 
-template <int D, bool PerSeq, bool Win>
+template <int D, bool PerSeq, bool Win, bool Rope>
 __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(PrefillGqaArgs a) {
   using Geo = FwdGeo<D>;
   constexpr int KB = Geo::KB, ROW = Geo::ROW, RPI = Geo::RPI, TILE = Geo::TILE;
@@ -152,6 +161,15 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(Prefi
     const uint16_t* qp = a.qkv + (static_cast<int64_t>(b) * a.T + t) * a.ld + hoff + 8 * hi;
 #pragma unroll
     for (int ks = 0; ks < Geo::NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
+    // Rope: k-step ks holds the low-half columns 16 ks + 8 hi + j, k-step ks + NKS / 2 their
+    // partners; the table row is the cache position of the token that was loaded
+    if constexpr (Rope) {
+      const int64_t p = static_cast<int64_t>(len) + t;
+      const float* cs = a.rope + (p < a.L_max ? p : a.L_max - 1) * D + 8 * hi;
+#pragma unroll
+      for (int ks = 0; ks < Geo::NKS / 2; ++ks)
+        rope_rotate8(qf[ks], qf[ks + Geo::NKS / 2], cs + 16 * ks, D / 2);
+    }
   }
   f32x16 o[Geo::NDT];
 #pragma unroll
@@ -310,12 +328,15 @@ __global__ void __launch_bounds__(kAttnThreads, 2) attn_prefill_gqa_kernel(Prefi
 
 bool mis(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; }
 
-// Win: `window` keys per token (>= 1; one that covers every token's prefix is no window)
-template <bool PerSeq, bool Win = false>
+// Win: `window` keys per token (>= 1; one that covers every token's prefix is no window). Rope:
+// `rope` is the cos | sin table (fp32 [>= L_max, D], 16-byte aligned)
+template <bool PerSeq, bool Win = false, bool Rope = false>
 int prefill_gqa_launch(const void* qkv, int64_t ld, const void* k_cache, const void* v_cache,
                        const void* length, void* out, int64_t ldo, int B, int T, int Hq, int Hkv,
-                       int D, int L_max, float scale, hipStream_t stream, int window = 0) {
+                       int D, int L_max, float scale, hipStream_t stream, int window = 0,
+                       const void* rope = nullptr) {
   if (D != 64 && D != 128) return hipErrorInvalidValue;
+  if (Rope && (!rope || mis(rope, 16))) return hipErrorInvalidValue;
   if (Win && window < 1) return hipErrorInvalidValue;
   if (B <= 0 || T <= 0 || Hkv <= 0 || Hq <= 0 || L_max <= 0 || !(scale > 0.f))
     return hipErrorInvalidValue;
@@ -333,14 +354,14 @@ int prefill_gqa_launch(const void* qkv, int64_t ld, const void* k_cache, const v
   PrefillGqaArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(k_cache),
                    static_cast<const uint16_t*>(v_cache), static_cast<const int*>(length),
                    static_cast<uint16_t*>(out), ld, ldo, B, T, Hkv, L_max, gsh,
-                   scale * 1.4426950408889634f, window};
+                   scale * 1.4426950408889634f, window, static_cast<const float*>(rope)};
   const int TB = kQB >> gsh;                       // tokens per workgroup
   const dim3 grid((T + TB - 1) / TB, Hkv, B);
   if (D == 64)
-    hipLaunchKernelGGL((attn_prefill_gqa_kernel<64, PerSeq, Win>), grid, dim3(kAttnThreads),
+    hipLaunchKernelGGL((attn_prefill_gqa_kernel<64, PerSeq, Win, Rope>), grid, dim3(kAttnThreads),
                        4 * FwdGeo<64>::TILE, stream, a);
   else
-    hipLaunchKernelGGL((attn_prefill_gqa_kernel<128, PerSeq, Win>), grid, dim3(kAttnThreads),
+    hipLaunchKernelGGL((attn_prefill_gqa_kernel<128, PerSeq, Win, Rope>), grid, dim3(kAttnThreads),
                        4 * FwdGeo<128>::TILE, stream, a);
   return hipGetLastError();
 }
@@ -397,4 +418,44 @@ DLBB_API int dlbb_attn_prefill_gqa_win_seq(const void* qkv, int64_t ld, const vo
                                            hipStream_t stream) {
   return prefill_gqa_launch<true, true>(qkv, ld, k_cache, v_cache, length, out, ldo, B, T, Hq,
                                         Hkv, D, L_max, scale, stream, window);
+}
+
+// The rotary forms (the file header, "Rotary position embedding"): the entry points above with
+// `rope`, the cos | sin table (fp32 [P >= L_max, D] contiguous, 16-byte aligned) after `length`.
+// Query token t is rotated at table row *length + t (length[b] + t); the block's K must have been
+// stored by dlbb_kv_append_gqa_rope* with the same table. A null or misaligned table returns
+// hipErrorInvalidValue before any launch.
+DLBB_API int dlbb_attn_prefill_gqa_rope(const void* qkv, int64_t ld, const void* k_cache,
+                                        const void* v_cache, const void* length, const void* rope,
+                                        void* out, int64_t ldo, int B, int T, int Hq, int Hkv,
+                                        int D, int L_max, float scale, hipStream_t stream) {
+  return prefill_gqa_launch<false, false, true>(qkv, ld, k_cache, v_cache, length, out, ldo, B, T,
+                                                Hq, Hkv, D, L_max, scale, stream, 0, rope);
+}
+
+DLBB_API int dlbb_attn_prefill_gqa_rope_seq(const void* qkv, int64_t ld, const void* k_cache,
+                                            const void* v_cache, const void* length,
+                                            const void* rope, void* out, int64_t ldo, int B, int T,
+                                            int Hq, int Hkv, int D, int L_max, float scale,
+                                            hipStream_t stream) {
+  return prefill_gqa_launch<true, false, true>(qkv, ld, k_cache, v_cache, length, out, ldo, B, T,
+                                               Hq, Hkv, D, L_max, scale, stream, 0, rope);
+}
+
+DLBB_API int dlbb_attn_prefill_gqa_win_rope(const void* qkv, int64_t ld, const void* k_cache,
+                                            const void* v_cache, const void* length,
+                                            const void* rope, void* out, int64_t ldo, int B, int T,
+                                            int Hq, int Hkv, int D, int L_max, int window,
+                                            float scale, hipStream_t stream) {
+  return prefill_gqa_launch<false, true, true>(qkv, ld, k_cache, v_cache, length, out, ldo, B, T,
+                                               Hq, Hkv, D, L_max, scale, stream, window, rope);
+}
+
+DLBB_API int dlbb_attn_prefill_gqa_win_rope_seq(const void* qkv, int64_t ld, const void* k_cache,
+                                                const void* v_cache, const void* length,
+                                                const void* rope, void* out, int64_t ldo, int B,
+                                                int T, int Hq, int Hkv, int D, int L_max,
+                                                int window, float scale, hipStream_t stream) {
+  return prefill_gqa_launch<true, true, true>(qkv, ld, k_cache, v_cache, length, out, ldo, B, T,
+                                              Hq, Hkv, D, L_max, scale, stream, window, rope);
 }

@@ -53,7 +53,11 @@
 // shapes with several token blocks; at the shapes this kernel is for (T G <= 128) there is ONE
 // token block per chunk and the question does not arise.
 //
-// The tile body repeats attn_prefill_gqa.hip's (that file stays as it is, bit for bit).
+// Rotary position embedding (the Rope instantiations, dlbb_attn_prefill_gqa_split_rope*):
+// attn_prefill_gqa.hip's rule. Every chunk's workgroup rotates its copy of Q in registers after the
+// gather, at table row min(len_b + min(token(lane), T - 1), L_max - 1); the combine is unchanged.
+//
+// The tile body repeats attn_prefill_gqa.hip's.
 #include "attn_tile.h"
 #include "common.h"
 
@@ -80,9 +84,10 @@ struct PrefillGqaSplitArgs {
   int gsh;                  // log2 G
   int n_chunks, chunk;
   float scale_log2;         // log2(e) * scale
+  const float* rope;        // Rope kernels: cos | sin rows [>= L_max, D] fp32
 };
 
-template <int D, bool PerSeq>
+template <int D, bool PerSeq, bool Rope>
 __global__ void __launch_bounds__(kAttnThreads, 2)
 attn_prefill_gqa_split_kernel(PrefillGqaSplitArgs a) {
   using Geo = FwdGeo<D>;
@@ -130,6 +135,15 @@ attn_prefill_gqa_split_kernel(PrefillGqaSplitArgs a) {
     const uint16_t* qp = a.qkv + (static_cast<int64_t>(b) * a.T + t) * a.ld + head * D + 8 * hi;
 #pragma unroll
     for (int ks = 0; ks < Geo::NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
+    // Rope: k-step ks holds the low-half columns 16 ks + 8 hi + j, k-step ks + NKS / 2 their
+    // partners; the table row is the cache position of the token that was loaded
+    if constexpr (Rope) {
+      const int64_t p = static_cast<int64_t>(len) + t;
+      const float* cs = a.rope + (p < a.L_max ? p : a.L_max - 1) * D + 8 * hi;
+#pragma unroll
+      for (int ks = 0; ks < Geo::NKS / 2; ++ks)
+        rope_rotate8(qf[ks], qf[ks + Geo::NKS / 2], cs + 16 * ks, D / 2);
+    }
   }
   f32x16 o[Geo::NDT];
 #pragma unroll
@@ -327,12 +341,15 @@ attn_prefill_gqa_combine_kernel(PrefillGqaSplitArgs a) {
 
 bool mis(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; }
 
-template <bool PerSeq>
+// Rope: `rope` is the cos | sin table (fp32 [>= L_max, D], 16-byte aligned)
+template <bool PerSeq, bool Rope = false>
 int prefill_gqa_split_launch(const void* qkv, int64_t ld, const void* k_cache,
                              const void* v_cache, const void* length, void* ws, void* out,
                              int64_t ldo, int B, int T, int Hq, int Hkv, int D, int L_max,
-                             int len_bound, int chunk, float scale, hipStream_t stream) {
+                             int len_bound, int chunk, float scale, hipStream_t stream,
+                             const void* rope = nullptr) {
   if (D != 64 && D != 128) return hipErrorInvalidValue;
+  if (Rope && (!rope || mis(rope, 16))) return hipErrorInvalidValue;
   if (B <= 0 || T <= 0 || Hkv <= 0 || Hq <= 0 || L_max <= 0 || !(scale > 0.f))
     return hipErrorInvalidValue;
   if (Hq % Hkv) return hipErrorInvalidValue;
@@ -360,17 +377,18 @@ int prefill_gqa_split_launch(const void* qkv, int64_t ld, const void* k_cache,
   PrefillGqaSplitArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(k_cache),
                         static_cast<const uint16_t*>(v_cache), static_cast<const int*>(length),
                         static_cast<float*>(ws), static_cast<uint16_t*>(out), ld, ldo, B, T, Hq,
-                        Hkv, L_max, gsh, n_chunks, chunk, scale * 1.4426950408889634f};
+                        Hkv, L_max, gsh, n_chunks, chunk, scale * 1.4426950408889634f,
+                        static_cast<const float*>(rope)};
   const dim3 grid(nblk, n_chunks * Hkv, B);
   const int rpb = kCombineThreads / (D / 4);
   const dim3 cgrid(static_cast<unsigned>((rows + rpb - 1) / rpb));
   if (D == 64) {
-    hipLaunchKernelGGL((attn_prefill_gqa_split_kernel<64, PerSeq>), grid, dim3(kAttnThreads),
+    hipLaunchKernelGGL((attn_prefill_gqa_split_kernel<64, PerSeq, Rope>), grid, dim3(kAttnThreads),
                        4 * FwdGeo<64>::TILE, stream, a);
     hipLaunchKernelGGL((attn_prefill_gqa_combine_kernel<64, PerSeq>), cgrid,
                        dim3(kCombineThreads), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((attn_prefill_gqa_split_kernel<128, PerSeq>), grid, dim3(kAttnThreads),
+    hipLaunchKernelGGL((attn_prefill_gqa_split_kernel<128, PerSeq, Rope>), grid, dim3(kAttnThreads),
                        4 * FwdGeo<128>::TILE, stream, a);
     hipLaunchKernelGGL((attn_prefill_gqa_combine_kernel<128, PerSeq>), cgrid,
                        dim3(kCombineThreads), 0, stream, a);
@@ -410,4 +428,31 @@ DLBB_API int dlbb_attn_prefill_gqa_split_seq(const void* qkv, int64_t ld, const 
                                              float scale, hipStream_t stream) {
   return prefill_gqa_split_launch<true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B, T, Hq,
                                         Hkv, D, L_max, len_bound, chunk, scale, stream);
+}
+
+// The rotary forms (the file header, "Rotary position embedding"): the entry points above with
+// `rope`, the cos | sin table (fp32 [P >= L_max, D] contiguous, 16-byte aligned) after `length`.
+// Query token t is rotated at table row *length + t (length[b] + t); the block's K must have been
+// stored by dlbb_kv_append_gqa_rope* with the same table. A null or misaligned table returns
+// hipErrorInvalidValue before any launch.
+DLBB_API int dlbb_attn_prefill_gqa_split_rope(const void* qkv, int64_t ld, const void* k_cache,
+                                              const void* v_cache, const void* length,
+                                              const void* rope, void* ws, void* out, int64_t ldo,
+                                              int B, int T, int Hq, int Hkv, int D, int L_max,
+                                              int len_bound, int chunk, float scale,
+                                              hipStream_t stream) {
+  return prefill_gqa_split_launch<false, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B,
+                                               T, Hq, Hkv, D, L_max, len_bound, chunk, scale,
+                                               stream, rope);
+}
+
+DLBB_API int dlbb_attn_prefill_gqa_split_rope_seq(const void* qkv, int64_t ld,
+                                                  const void* k_cache, const void* v_cache,
+                                                  const void* length, const void* rope, void* ws,
+                                                  void* out, int64_t ldo, int B, int T, int Hq,
+                                                  int Hkv, int D, int L_max, int len_bound,
+                                                  int chunk, float scale, hipStream_t stream) {
+  return prefill_gqa_split_launch<true, true>(qkv, ld, k_cache, v_cache, length, ws, out, ldo, B,
+                                              T, Hq, Hkv, D, L_max, len_bound, chunk, scale,
+                                              stream, rope);
 }

@@ -74,4 +74,30 @@ __device__ __forceinline__ int kswz_d(int r) { return D == 64 ? kswz(r) : (r & 1
 template <int D>
 __device__ __forceinline__ int vswz_d(int r) { return D == 64 ? vswz(r) : ((r & 3) << 2); }
 
+// Rotary position embedding of the grouped-query kernels (attn_decode_gqa.hip, attn_prefill_gqa*),
+// rotate-half (NeoX / HF Llama) pairing: column i < D / 2 of a Q or K row is paired with column
+// i + D / 2. The angles come from a table: row p of `rope` (fp32 [P, D], 16-byte aligned) holds
+// cos in [0, D / 2) and sin in [D / 2, D) for cache position p, so every scaling scheme is the
+// table builder's business and the kernels compute no trigonometry. rope_rotate8 rotates 8
+// columns c .. c + 7 of the low half (`lo`) with their partners (`hi`); `cs` points at the row's
+// cos of column c (c a multiple of 8), its sin is `half` = D / 2 floats further:
+//   lo' = lo cos - hi sin, hi' = hi cos + lo sin, in fp32, each rounded to bf16 once.
+// V is u16x8 (a cache row on its way through the append) or bf16x8 (a Q fragment held for the
+// MFMAs). With cos = 1, sin = 0 every finite value comes back with its bits.
+template <typename V>
+__device__ __forceinline__ void rope_rotate8(V& lo, V& hi, const float* cs, int half) {
+  const f32x4 c0 = *reinterpret_cast<const f32x4*>(cs);
+  const f32x4 c1 = *reinterpret_cast<const f32x4*>(cs + 4);
+  const f32x4 s0 = *reinterpret_cast<const f32x4*>(cs + half);
+  const f32x4 s1 = *reinterpret_cast<const f32x4*>(cs + half + 4);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float c = j < 4 ? c0[j & 3] : c1[j & 3], s = j < 4 ? s0[j & 3] : s1[j & 3];
+    const float l = bf16_to_f32(static_cast<uint16_t>(lo[j]));
+    const float h = bf16_to_f32(static_cast<uint16_t>(hi[j]));
+    lo[j] = f32_to_bf16(__builtin_fmaf(l, c, -(h * s)));
+    hi[j] = f32_to_bf16(__builtin_fmaf(h, c, l * s));
+  }
+}
+
 }  // namespace dlbb

@@ -278,6 +278,48 @@ _SIGS = {
                                                 c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                                 c_int, c_int, c_int, c_int, c_int, c_float,
                                                 c_void_p]),
+    # the rotary forms of the grouped-query kernels: the cos | sin table pointer after `length`
+    "dlbb_kv_append_gqa_rope": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dlbb_kv_append_gqa_rope_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_void_p]),
+    "dlbb_attn_decode_gqa_rope": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                          c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "dlbb_attn_decode_gqa_rope_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                              c_int, c_int, c_int, c_int, c_int, c_float,
+                                              c_void_p]),
+    "dlbb_attn_decode_gqa_win_rope": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                              c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                              c_void_p]),
+    "dlbb_attn_decode_gqa_win_rope_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                                  c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                  c_float, c_void_p]),
+    "dlbb_attn_prefill_gqa_rope": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                           c_int, c_int, c_float, c_void_p]),
+    "dlbb_attn_prefill_gqa_rope_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                               c_int, c_int, c_int, c_float, c_void_p]),
+    "dlbb_attn_prefill_gqa_win_rope": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                               c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "dlbb_attn_prefill_gqa_win_rope_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_int64, c_int, c_int,
+                                                   c_int, c_int, c_int, c_int, c_int, c_float,
+                                                   c_void_p]),
+    "dlbb_attn_prefill_gqa_split_rope": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                                 c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                 c_float, c_void_p]),
+    "dlbb_attn_prefill_gqa_split_rope_seq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_int64, c_int, c_int, c_int, c_int, c_int,
+                                                     c_int, c_int, c_int, c_float, c_void_p]),
     "dlbb_rccl_unique_id_bytes": (c_int, []),
     "dlbb_rccl_get_unique_id": (c_int, [c_void_p]),
     "dlbb_rccl_init": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),

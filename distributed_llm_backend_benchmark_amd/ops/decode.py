@@ -184,6 +184,27 @@ Grouped-query heads (opt-in, ``n_kv_head=`` on :func:`kv_append` / :func:`decode
   a long prefix walks the tiles of ``W + T`` keys without a key split. The torch forms slice
   (decode) or band-mask (prefill) the same keys. ``ValueError``: ``window < 1``, a window on
   ungrouped heads, a window with ``key_split``.
+* Rotary position embedding (opt-in, ``rope=`` on :func:`kv_append`, :func:`decode_attention` and
+  :func:`prefill_attention` with grouped heads; the ``dlbb_*_gqa*_rope*`` entry points). ``rope`` is
+  an fp32 contiguous table ``[P, D]`` on ``qkv``'s device, ``P >= L_max``: ``rope[p, :D/2]`` is
+  ``cos`` and ``rope[p, D/2:]`` is ``sin`` of the ``D/2`` angles at cache position ``p``. A table
+  covers every scaling scheme (linear, NTK, YaRN, Llama-3); the kernels compute no trigonometry
+  and nothing here builds one (``inv = theta ** (-arange(D/2) / (D/2))``, ``ang = p * inv``,
+  ``cat(cos(ang), sin(ang))`` is the plain one). The pairing is rotate-half (NeoX / HF Llama):
+  with ``lo = x[:D/2]``, ``hi = x[D/2:]`` a row at position ``p`` becomes ``lo' = lo cos[p] - hi
+  sin[p]``, ``hi' = hi cos[p] + lo sin[p]``, computed in fp32 and rounded to bf16 once.
+  :func:`kv_append` stores every K row rotated at its own position (``length + t``, per row for a
+  per-sequence ``length``) and V untouched, so the cache holds rotated keys and nothing rotates a
+  key again. :func:`decode_attention` appends that way and rotates Q at ``length`` inside the
+  split kernel; :func:`prefill_attention` rotates query token ``t`` at ``length + t`` inside the
+  one-launch kernel (with or without ``window``) and the ``key_split`` kernel. The rotation is in
+  registers right after the Q loads (a lane holds both columns of a pair): no launch, no LDS and
+  no pass over the activation are added. Positions are absolute under a ``window``. ``None`` is
+  the calls above, launch for launch; a table of ``cos = 1, sin = 0`` gives their bits. The torch
+  forms rotate the same way. ``ValueError`` (before any launch, nothing written): ``rope`` on
+  ungrouped heads, a table that is not fp32, not contiguous, not ``D`` wide, shorter than
+  ``L_max`` or on another device. Not built: the GPT-J interleaved pairing, partial rotary
+  dimensions, ``rope`` on the ungrouped, paged, FP8 or MXFP4 kernels.
 * Not built: paged and FP8 grouped caches (``ValueError``), an automatic choice between the split
   and the one-launch prefill, a fused append, GQA in the models; for the window: a rolling (ring)
   cache that stores only ``W`` rows, attention sinks, a window on the ungrouped, paged, FP8 or
@@ -744,12 +765,50 @@ def _views_gqa(qkv: torch.Tensor, n_head: int, n_kv_head: int):
     return x[:, :n_head], x[:, n_head:n_head + n_kv_head], x[:, n_head + n_kv_head:]
 
 
+def _rope(what: str, rope: Optional[torch.Tensor], n_kv_head: Optional[int], qkv, k_cache):
+    """The ``rope=`` table of a call, checked (module docstring, "Rotary position embedding");
+    ``ValueError`` naming ``rope`` for one on ungrouped heads (``n_kv_head`` as :func:`_kv_heads`
+    returned it) or one that is not fp32 contiguous ``[P >= L_max, D]`` on ``qkv``'s device."""
+    if rope is None:
+        return None
+    if n_kv_head is None:
+        raise ValueError(f"{what}: rope= goes with grouped heads (n_kv_head < n_head); the "
+                         "ungrouped kernels have no rotary form")
+    L_max, D = k_cache.shape[2:] if k_cache.dim() == 4 else (-1, -1)
+    if rope.dtype != torch.float32:
+        raise ValueError(f"{what}: the rope table is fp32, got {rope.dtype}")
+    if rope.dim() != 2 or rope.shape[1] != D:
+        raise ValueError(f"{what}: the rope table is [P, D = {D}] (cos | sin), got "
+                         f"{tuple(rope.shape)}")
+    if not rope.is_contiguous():
+        raise ValueError(f"{what}: the rope table must be contiguous")
+    if rope.shape[0] < L_max:
+        raise ValueError(f"{what}: the rope table has {rope.shape[0]} rows for a cache of "
+                         f"{L_max} positions")
+    if rope.device != qkv.device:
+        raise ValueError(f"{what}: the rope table is on {rope.device}, qkv on {qkv.device}")
+    return rope
+
+
+def _rotate(x: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """``x [..., T, D]`` rotated by the table rows ``[T, D]`` (cos | sin) of its ``T`` positions,
+    rotate-half pairing, in fp32, rounded to ``x``'s dtype once."""
+    half = x.shape[-1] // 2
+    lo, hi = x[..., :half].float(), x[..., half:].float()
+    cos, sin = rows[:, :half], rows[:, half:]
+    return torch.cat((lo * cos - hi * sin, hi * cos + lo * sin), -1).to(x.dtype)
+
+
 def torch_kv_append(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
-                    v_scale=None, n_kv_head: Optional[int] = None) -> None:
-    """Torch form of :func:`kv_append` at the host position ``pos``."""
+                    v_scale=None, n_kv_head: Optional[int] = None,
+                    rope: Optional[torch.Tensor] = None) -> None:
+    """Torch form of :func:`kv_append` at the host position ``pos``. ``rope`` (grouped layout
+    only): the K rows are stored rotated by table rows ``[pos, pos + T)``."""
     T = qkv.shape[1]
     if n_kv_head is not None:                   # grouped layout: the bf16 cache only
         _, k, v = _views_gqa(qkv, n_head, n_kv_head)
+        if rope is not None:
+            k = _rotate(k, rope[pos:pos + T])
         k_cache[:, :, pos:pos + T] = k
         v_cache[:, :, pos:pos + T] = v
         return
@@ -787,15 +846,19 @@ def dequantize(cache: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 def torch_decode_attention(qkv, n_head: int, k_cache, v_cache, pos: int, k_scale=None,
                            v_scale=None, n_kv_head: Optional[int] = None,
-                           window: Optional[int] = None) -> torch.Tensor:
+                           window: Optional[int] = None,
+                           rope: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Torch form of :func:`decode_attention` at the host position ``pos`` (not replayable
     across positions: the slice bound is a host value). ``n_kv_head``: the grouped layout; K / V
     are expanded to the query heads with ``repeat_interleave`` for SDPA. ``window`` (grouped
-    layout only): the keys are the slice ``[max(0, pos + 1 - window), pos + 1)``."""
+    layout only): the keys are the slice ``[max(0, pos + 1 - window), pos + 1)``. ``rope``
+    (grouped layout only): K is stored and Q attends rotated by table row ``pos``."""
     B, _, C3 = qkv.shape
     if n_kv_head is not None:
-        torch_kv_append(qkv, n_head, k_cache, v_cache, pos, n_kv_head=n_kv_head)
+        torch_kv_append(qkv, n_head, k_cache, v_cache, pos, n_kv_head=n_kv_head, rope=rope)
         q, _, _ = _views_gqa(qkv, n_head, n_kv_head)
+        if rope is not None:
+            q = _rotate(q, rope[pos:pos + 1])
         G = n_head // n_kv_head
         lo = 0 if window is None else max(0, pos + 1 - window)
         o = F.scaled_dot_product_attention(
@@ -833,7 +896,8 @@ def _host_positions(length: torch.Tensor, pos) -> List[int]:
 
 
 def torch_kv_append_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int], k_scale=None,
-                        v_scale=None, n_kv_head: Optional[int] = None) -> None:
+                        v_scale=None, n_kv_head: Optional[int] = None,
+                        rope: Optional[torch.Tensor] = None) -> None:
     """Torch form of the per-sequence :func:`kv_append`: row ``b`` is copied at the host position
     ``pos[b]``; nothing for an empty slot (``pos[b] < 0``)."""
     for b, p in enumerate(pos):
@@ -841,12 +905,13 @@ def torch_kv_append_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int], 
             continue
         torch_kv_append(qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p,
                         None if k_scale is None else k_scale[b:b + 1],
-                        None if v_scale is None else v_scale[b:b + 1], n_kv_head)
+                        None if v_scale is None else v_scale[b:b + 1], n_kv_head, rope)
 
 
 def torch_decode_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int],
                                k_scale=None, v_scale=None, n_kv_head: Optional[int] = None,
-                               window: Optional[int] = None) -> torch.Tensor:
+                               window: Optional[int] = None,
+                               rope: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Torch form of the per-sequence :func:`decode_attention` at the host positions ``pos``:
     row ``b`` is :func:`torch_decode_attention` on the batch-1 slice of its cache at ``pos[b]``,
     so a row has the bits of the shared-length form; empty slots give zero rows. (One SDPA over
@@ -861,7 +926,7 @@ def torch_decode_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence
         out[b:b + 1] = torch_decode_attention(
             qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p,
             None if k_scale is None else k_scale[b:b + 1],
-            None if v_scale is None else v_scale[b:b + 1], n_kv_head, window)
+            None if v_scale is None else v_scale[b:b + 1], n_kv_head, window, rope)
     return out
 
 
@@ -1133,7 +1198,8 @@ def _decode_attention_paged(qkv, n_head, k_pool, v_pool, length, len_bound, work
 def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
                             keep: Optional[torch.Tensor] = None, k_scale=None,
                             v_scale=None, n_kv_head: Optional[int] = None,
-                            window: Optional[int] = None) -> torch.Tensor:
+                            window: Optional[int] = None,
+                            rope: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Torch form of :func:`prefill_attention` at the host position ``pos``: fp32 SDPA of the
     ``T`` queries over ``cache[:, :, :pos + T]`` (the chunk already appended; an FP8 cache is
     dequantised with :func:`dequantize`) under an explicit bottom-right causal mask: query ``i``
@@ -1142,12 +1208,15 @@ def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
     stale reaches the product. ``n_kv_head``: the grouped layout (the bf16 cache only); the live
     cache rows are expanded to the query heads with ``repeat_interleave`` in fp32. ``window``
     (grouped layout only): the band ``pos + i - window < key`` on top of the causal mask, over the
-    cache rows from the first token's bound on."""
+    cache rows from the first token's bound on. ``rope`` (grouped layout only): query ``i`` is
+    rotated by table row ``pos + i`` (the cache holds keys rotated on their way in)."""
     B, T, C3 = qkv.shape
     n = min(pos + T, k_cache.shape[2])
     mask = torch.ones(T, n, dtype=torch.bool, device=qkv.device).tril(diagonal=pos)
     if n_kv_head is not None:
         q, _, _ = _views_gqa(qkv, n_head, n_kv_head)
+        if rope is not None:
+            q = _rotate(q, rope[pos:pos + T])
         G = n_head // n_kv_head
         lo = 0                                  # rows below the first token's window: not read
         if window is not None:
@@ -1173,7 +1242,8 @@ def torch_prefill_attention(qkv, n_head: int, k_cache, v_cache, pos: int,
 
 def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequence[int],
                                 k_scale=None, v_scale=None, n_kv_head: Optional[int] = None,
-                                window: Optional[int] = None) -> torch.Tensor:
+                                window: Optional[int] = None,
+                                rope: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Torch form of the per-sequence :func:`prefill_attention`: row ``b`` is
     :func:`torch_prefill_attention` on its batch-1 slice at ``pos[b]``; empty slots give zero
     rows."""
@@ -1185,7 +1255,7 @@ def torch_prefill_attention_seq(qkv, n_head: int, k_cache, v_cache, pos: Sequenc
             out[b:b + 1] = torch_prefill_attention(
                 qkv[b:b + 1], n_head, k_cache[b:b + 1], v_cache[b:b + 1], p, None,
                 None if k_scale is None else k_scale[b:b + 1],
-                None if v_scale is None else v_scale[b:b + 1], n_kv_head, window)
+                None if v_scale is None else v_scale[b:b + 1], n_kv_head, window, rope)
     return out
 
 
@@ -1226,7 +1296,8 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                       n_kv_head: Optional[int] = None, key_split: Optional[int] = None,
                       len_bound: Optional[int] = None,
                       workspace: Optional[torch.Tensor] = None,
-                      window: Optional[int] = None) -> torch.Tensor:
+                      window: Optional[int] = None,
+                      rope: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Chunked prefill (``csrc/attn_prefill.hip``): causal attention of a block of ``T`` new
     tokens over the cache, ``qkv [B, T, 3C]`` -> ``[B, T, C]``. The block's K / V must already be
     in the cache at ``[length, length + T)`` (:func:`kv_append`) and ``length`` not yet advanced;
@@ -1265,11 +1336,17 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     keys, itself included: positions ``max(0, length_b + i - window + 1) .. length_b + i``. The
     one-launch kernel starts at the tile that holds the first key of a workgroup's first token,
     so a short block over a long prefix costs the tiles of ``window + T`` keys. A window that
-    covers every token's prefix gives the bits of the call without one."""
+    covers every token's prefix gives the bits of the call without one.
+
+    ``rope`` (grouped heads only; None = no rotation, call for call): the fp32 ``cos | sin`` table
+    ``[P >= L_max, D]`` (module docstring, "Rotary position embedding"): query token ``t`` is
+    rotated in registers at table row ``length_b + t``. The block's K must have been appended by
+    :func:`kv_append` with the same table. It goes with ``window`` and with ``key_split``."""
     if qkv.dim() != 3 or qkv.shape[1] < 1:
         raise ValueError(f"prefill_attention takes qkv [B, T >= 1, 3C], got {tuple(qkv.shape)}")
     n_kv_head = _kv_heads(n_head, n_kv_head)
     window = _window("prefill_attention", window, n_kv_head)
+    rope = _rope("prefill_attention", rope, n_kv_head, qkv, k_cache)
     if window is not None and key_split is not None:
         raise ValueError("prefill_attention: the key-split kernel has no window (window= goes "
                          "with the one-launch kernel, which visits the window's tiles only)")
@@ -1285,7 +1362,7 @@ def prefill_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     if n_kv_head is not None:
         _gqa_check("prefill_attention", k_cache, v_cache, k_scale, v_scale, block_table)
         return _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos,
-                                      key_split, len_bound, workspace, window)
+                                      key_split, len_bound, workspace, window, rope)
     _no_mxfp4("prefill_attention", "prefill over an MXFP4 cache", k_cache, v_cache, k_scale,
               v_scale)
     fp8 = _check_fp8_cache(k_cache, v_cache, k_scale, v_scale)
@@ -1360,16 +1437,19 @@ def _gqa_hip(what: str, qkv, n_head: int, n_kv_head: int, k_cache, v_cache) -> b
     return True
 
 
-def _hip_append_gqa(qkv, n_head: int, n_kv_head: int, k_cache, v_cache, length, T: int) -> None:
+def _hip_append_gqa(qkv, n_head: int, n_kv_head: int, k_cache, v_cache, length, T: int,
+                    rope=None) -> None:
     B, _, W = qkv.shape
-    name = "dlbb_kv_append_gqa" + ("_seq" if length.numel() != 1 else "")
+    name = "dlbb_kv_append_gqa" + ("" if rope is None else "_rope") + \
+        ("_seq" if length.numel() != 1 else "")
     fn = getattr(_lib.lib(), name)
-    check(fn(qkv.data_ptr(), W, k_cache.data_ptr(), v_cache.data_ptr(), length.data_ptr(), B, T,
-             n_head, n_kv_head, W // (n_head + 2 * n_kv_head), k_cache.shape[2],
+    table = () if rope is None else (rope.data_ptr(),)
+    check(fn(qkv.data_ptr(), W, k_cache.data_ptr(), v_cache.data_ptr(), length.data_ptr(), *table,
+             B, T, n_head, n_kv_head, W // (n_head + 2 * n_kv_head), k_cache.shape[2],
              _lib.stream(qkv.device)), name[5:])
 
 
-def _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos) -> None:
+def _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos, rope=None) -> None:
     """:func:`kv_append` on the grouped layout (module docstring, "Grouped-query heads")."""
     T, L_max = qkv.shape[1], k_cache.shape[2]
     seq = _per_sequence(length, qkv.shape[0], "kv_append")
@@ -1380,7 +1460,7 @@ def _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos) -> Non
             raise ValueError(f"kv_append: position {max(host)} + {T} tokens > cache length "
                              f"{L_max}")
     if _gqa_hip("kv_append", qkv, n_head, n_kv_head, k_cache, v_cache):
-        _hip_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, T)
+        _hip_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, T, rope)
         return
     if host is None:
         host = _host_positions(length, None) if seq else [_host_pos(length, None)]
@@ -1388,16 +1468,16 @@ def _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos) -> Non
             raise ValueError(f"kv_append: position {max(host)} + {T} tokens > cache length "
                              f"{L_max}")
     if seq:
-        torch_kv_append_seq(qkv, n_head, k_cache, v_cache, host, n_kv_head=n_kv_head)
+        torch_kv_append_seq(qkv, n_head, k_cache, v_cache, host, n_kv_head=n_kv_head, rope=rope)
     else:
-        torch_kv_append(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head)
+        torch_kv_append(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head, rope=rope)
 
 
 def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_bound, workspace,
-                          pos, chunk, fused, window=None):
+                          pos, chunk, fused, window=None, rope=None):
     """:func:`decode_attention` on the grouped layout: the GQA append launch, then the split over
     the KV heads and the combine (``csrc/attn_decode_gqa.hip``); with ``window`` their ``_win``
-    entry points."""
+    entry points, with ``rope`` the ``_rope`` ones of the append and the split."""
     what = "decode_attention"
     if fused:
         raise ValueError(f"{what}: the grouped-query kernels have no fused append")
@@ -1427,12 +1507,13 @@ def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_
         elif workspace.numel() < need or workspace.dtype != torch.float32:
             raise ValueError(f"{what}: workspace of {workspace.numel()} fp32 < {need}")
         out = torch.empty(B, 1, C, dtype=qkv.dtype, device=qkv.device)
-        _hip_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, 1)
+        _hip_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, 1, rope)
         name = "dlbb_attn_decode_gqa" + ("" if window is None else "_win") + \
-            ("_seq" if seq else "")
+            ("" if rope is None else "_rope") + ("_seq" if seq else "")
         win = () if window is None else (min(window, L_max),)
+        table = () if rope is None else (rope.data_ptr(),)
         check(getattr(_lib.lib(), name)(qkv.data_ptr(), qkv.shape[2], k_cache.data_ptr(),
-                                        v_cache.data_ptr(), length.data_ptr(),
+                                        v_cache.data_ptr(), length.data_ptr(), *table,
                                         workspace.data_ptr(), out.data_ptr(), C, B, n_head,
                                         n_kv_head, D, L_max, bound, chunk, *win,
                                         1.0 / math.sqrt(D), _lib.stream(qkv.device)), name[5:])
@@ -1443,19 +1524,20 @@ def _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_
             raise ValueError(f"{what}: position {max(host)} + 1 > cache length {L_max}")
     if seq:
         return torch_decode_attention_seq(qkv, n_head, k_cache, v_cache, host,
-                                          n_kv_head=n_kv_head, window=window)
+                                          n_kv_head=n_kv_head, window=window, rope=rope)
     return torch_decode_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head,
-                                  window=window)
+                                  window=window, rope=rope)
 
 
 def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos,
-                           key_split=None, len_bound=None, workspace=None, window=None):
+                           key_split=None, len_bound=None, workspace=None, window=None,
+                           rope=None):
     """:func:`prefill_attention` on the grouped layout: one launch of
     ``csrc/attn_prefill_gqa.hip``, whose workgroups take the (token, query head) rows of one KV
     head, so a K / V tile is staged once for the ``G`` heads sharing it. With ``key_split`` (a
     chunk in keys, checked by the caller) the split and combine launches of
     ``csrc/attn_prefill_gqa_split.hip`` instead; with ``window`` (never both) the ``_win`` entry
-    points of the one-launch kernel."""
+    points of the one-launch kernel; with ``rope`` the ``_rope`` form of whichever it is."""
     what = "prefill_attention"
     B, T, W = qkv.shape
     L_max = k_cache.shape[2]
@@ -1479,22 +1561,23 @@ def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos
     if _gqa_hip(what, qkv, n_head, n_kv_head, k_cache, v_cache):
         C = n_head * D
         out = torch.empty(B, T, C, dtype=qkv.dtype, device=qkv.device)
+        sfx = ("" if rope is None else "_rope") + ("_seq" if seq else "")
+        table = () if rope is None else (rope.data_ptr(),)
         if key_split is not None:
             if workspace is None:
                 workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
-            name = "dlbb_attn_prefill_gqa_split" + ("_seq" if seq else "")
+            name = "dlbb_attn_prefill_gqa_split" + sfx
             check(getattr(_lib.lib(), name)(qkv.data_ptr(), W, k_cache.data_ptr(),
-                                            v_cache.data_ptr(), length.data_ptr(),
+                                            v_cache.data_ptr(), length.data_ptr(), *table,
                                             workspace.data_ptr(), out.data_ptr(), C, B, T,
                                             n_head, n_kv_head, D, L_max, bound, chunk,
                                             1.0 / math.sqrt(D), _lib.stream(qkv.device)),
                   name[5:])
             return out
-        name = "dlbb_attn_prefill_gqa" + ("" if window is None else "_win") + \
-            ("_seq" if seq else "")
+        name = "dlbb_attn_prefill_gqa" + ("" if window is None else "_win") + sfx
         win = () if window is None else (min(window, 2 ** 31 - 1),)     # a C int
         check(getattr(_lib.lib(), name)(qkv.data_ptr(), W, k_cache.data_ptr(), v_cache.data_ptr(),
-                                        length.data_ptr(), out.data_ptr(), C, B, T, n_head,
+                                        length.data_ptr(), *table, out.data_ptr(), C, B, T, n_head,
                                         n_kv_head, D, L_max, *win, 1.0 / math.sqrt(D),
                                         _lib.stream(qkv.device)), name[5:])
         return out
@@ -1504,9 +1587,9 @@ def _prefill_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos
             raise ValueError(f"{what}: position {max(host)} + {T} tokens > cache length {L_max}")
     if seq:
         return torch_prefill_attention_seq(qkv, n_head, k_cache, v_cache, host,
-                                           n_kv_head=n_kv_head, window=window)
+                                           n_kv_head=n_kv_head, window=window, rope=rope)
     return torch_prefill_attention(qkv, n_head, k_cache, v_cache, host[0], n_kv_head=n_kv_head,
-                                   window=window)
+                                   window=window, rope=rope)
 
 
 def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: torch.Tensor,
@@ -1515,7 +1598,8 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
               v_scale: Optional[torch.Tensor] = None,
               block_table: Optional[torch.Tensor] = None, table_host=None,
               max_len: Optional[int] = None, n_keep: Optional[Sequence[int]] = None,
-              n_kv_head: Optional[int] = None) -> None:
+              n_kv_head: Optional[int] = None,
+              rope: Optional[torch.Tensor] = None) -> None:
     """K / V rows of ``qkv [B, T, 3C]`` -> cache positions ``[length, length + T)``. ``pos``:
     the host's copy of ``length`` (raises before launch on overflow; None on the HIP path = no
     host check, the kernel drops positions past the cache). ``k_scale`` / ``v_scale``: the row
@@ -1532,11 +1616,16 @@ def kv_append(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor, v_cache: to
 
     ``n_kv_head`` (None or ``n_head`` = one KV head per query head, the paths above): the
     grouped-query layout (module docstring): ``qkv`` is ``[B, T, (n_head + 2 n_kv_head) * D]`` and
-    the caches hold ``n_kv_head`` heads; bf16 contiguous caches only."""
+    the caches hold ``n_kv_head`` heads; bf16 contiguous caches only.
+
+    ``rope`` (grouped heads only; None = no rotation, call for call): the fp32 ``cos | sin`` table
+    ``[P >= L_max, D]`` (module docstring, "Rotary position embedding"): every K row is stored
+    rotated at its own cache position, the V rows untouched."""
     n_kv_head = _kv_heads(n_head, n_kv_head)
+    rope = _rope("kv_append", rope, n_kv_head, qkv, k_cache)
     if n_kv_head is not None:
         _gqa_check("kv_append", k_cache, v_cache, k_scale, v_scale, block_table)
-        return _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos)
+        return _kv_append_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, pos, rope)
     if block_table is not None:
         return _kv_append_paged(qkv, n_head, k_cache, v_cache, length, pos, k_scale, v_scale,
                                 block_table, table_host, max_len, n_keep)
@@ -1579,7 +1668,8 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
                      block_table: Optional[torch.Tensor] = None, table_host=None,
                      max_len: Optional[int] = None,
                      n_kv_head: Optional[int] = None,
-                     window: Optional[int] = None) -> torch.Tensor:
+                     window: Optional[int] = None,
+                     rope: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One decode step of causal attention: ``qkv [B, 1, 3C]`` -> ``[B, 1, C]``; the token's
     K / V are stored at cache position ``length`` and the query attends over ``length + 1``
     keys. ``length`` is not advanced.
@@ -1616,15 +1706,21 @@ def decode_attention(qkv: torch.Tensor, n_head: int, k_cache: torch.Tensor,
     from the window's first key, so the grid, the K / V bytes read and the workspace needed
     (:func:`workspace_numel` at ``min(len_bound, window)``) are those of a step over ``window``
     keys at any context length. A window at or over ``length + 1`` gives the bits of the call
-    without one."""
+    without one.
+
+    ``rope`` (grouped heads only; None = no rotation, call for call): the fp32 ``cos | sin`` table
+    ``[P >= L_max, D]`` (module docstring, "Rotary position embedding"): the step stores the
+    token's K rotated at position ``length`` and the split kernel rotates Q in registers at the
+    same position (the absolute one under a ``window`` too); no launch is added."""
     if qkv.dim() != 3 or qkv.shape[1] != 1:
         raise ValueError(f"decode_attention takes qkv [B, 1, 3C], got {tuple(qkv.shape)}")
     n_kv_head = _kv_heads(n_head, n_kv_head)
     window = _window("decode_attention", window, n_kv_head)
+    rope = _rope("decode_attention", rope, n_kv_head, qkv, k_cache)
     if n_kv_head is not None:
         _gqa_check("decode_attention", k_cache, v_cache, k_scale, v_scale, block_table)
         return _decode_attention_gqa(qkv, n_head, n_kv_head, k_cache, v_cache, length, len_bound,
-                                     workspace, pos, chunk, fused, window)
+                                     workspace, pos, chunk, fused, window, rope)
     if block_table is not None:
         return _decode_attention_paged(qkv, n_head, k_cache, v_cache, length, len_bound,
                                        workspace, pos, chunk, fused, k_scale, v_scale,

@@ -26,7 +26,12 @@ and ``len_bound`` = the live length; on the B 1 rows also at chunks 128 / 256 / 
 ``--prefill --gqa --window W``: the sliding-window form (``window=W``): T 8 / 128 over a prefix of
 8192 keys, ``gqa_window`` beside the unwindowed one-launch kernel (``gqa``), the key-split kernel
 (``gqa_split``), ``expanded`` and ``kv_copy_window``, a copy of the ``W + T`` K + V rows the window
-spans (default ``profiles/gqa_window/attn_prefill_gqa_window.jsonl``)."""
+spans (default ``profiles/gqa_window/attn_prefill_gqa_window.jsonl``).
+
+``--prefill --gqa --rope``: append + attend of 8 tokens over 8192 keys with ``rope=`` (``fused``)
+beside the same calls without RoPE (``plain``) and beside ``qkv`` rotated in torch first
+(``torch_rope``), one-launch and key-split (default
+``profiles/gqa_rope/attn_prefill_gqa_rope.jsonl``)."""
 import argparse
 import json
 import os
@@ -249,6 +254,69 @@ def prefill_gqa_rows(out_path, rounds=7, split=False, window=None):
                         fh.flush()
 
 
+def prefill_gqa_rope_rows(out_path, rounds=7):
+    """``--prefill --gqa --rope``: append + attend of a block of 8 tokens over 8192 keys at H_q 32,
+    D 128, through the one-launch kernel and through ``key_split=CHUNK_PREFILL_GQA``: ``fused``
+    (``rope=`` on both calls), ``plain`` (today's calls, no RoPE) and ``torch_rope`` (``qkv``
+    rotated in torch, then ``plain``), one timed window of each per round, round by round."""
+    import statistics
+
+    from decode_bench import rope_qkv_torch, rope_table
+    from distributed_llm_backend_benchmark_amd.ops import (CHUNK_PREFILL_GQA, kv_append,
+                                                           prefill_attention,
+                                                           prefill_workspace_numel)
+
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    HQ, D, T, prefix = 32, 128, 8, 8192
+    n = prefix + T
+    rope = rope_table(n, D, "cuda")
+    with open(out_path, "w") as fh:
+        for HKV in (8, 4):
+            for B in (1, 8):
+                for split in (False, True):
+                    qkv = torch.randn(B, T, (HQ + 2 * HKV) * D, device="cuda",
+                                      generator=gen).bfloat16()
+                    kc = torch.randn(B, HKV, n, D, device="cuda", generator=gen).bfloat16()
+                    vc = torch.randn(B, HKV, n, D, device="cuda", generator=gen).bfloat16()
+                    length = torch.tensor([prefix], dtype=torch.int32, device="cuda")
+                    kw = {"n_kv_head": HKV}
+                    if split:
+                        ws = torch.empty(prefill_workspace_numel(B, HQ, D, T, n,
+                                                                 CHUNK_PREFILL_GQA), device="cuda")
+                        kw.update(key_split=CHUNK_PREFILL_GQA, len_bound=n, workspace=ws)
+
+                    def block(x, **r):
+                        kv_append(x, HQ, kc, vc, length, n_kv_head=HKV, **r)
+                        return prefill_attention(x, HQ, kc, vc, length, **kw, **r)
+
+                    fns = {"plain": lambda: block(qkv), "fused": lambda: block(qkv, rope=rope),
+                           "torch_rope": lambda: block(rope_qkv_torch(qkv, HQ + HKV, D,
+                                                                      rope[prefix:n]))}
+                    err = float((fns["fused"]().float() - fns["torch_rope"]().float())
+                                .abs().max())
+                    iters = {k: max(10, min(2000, int(0.02 / t_best(fn, iters=5, rounds=1))))
+                             for k, fn in fns.items()}
+                    times = {k: [] for k in fns}
+                    for _ in range(rounds):                     # interleaved: one round of each
+                        for k, fn in fns.items():
+                            times[k].append(t_best(fn, iters=iters[k], rounds=1) * 1e6)
+                    med = {k: statistics.median(v) for k, v in times.items()}
+                    rec = {"H_q": HQ, "H_kv": HKV, "D": D, "B": B, "T": T, "prefix": prefix,
+                           "key_split": CHUNK_PREFILL_GQA if split else None,
+                           "max_abs_diff_fused_vs_torch_rope": err,
+                           "fused_over_plain": med["fused"] / med["plain"],
+                           "plain_spread": [min(times["plain"]) / med["plain"],
+                                            max(times["plain"]) / med["plain"]],
+                           "fused_over_torch_rope": med["fused"] / med["torch_rope"]}
+                    for k, v in times.items():
+                        rec.update({f"us_{k}": med[k], f"us_{k}_min": min(v),
+                                    f"us_{k}_max": max(v)})
+                    print(json.dumps(rec), flush=True)
+                    fh.write(json.dumps(rec) + "\n")
+                    fh.flush()
+
+
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--prefill", action="store_true")
 _ap.add_argument("--fp8", action="store_true", help="with --prefill: the FP8-cache rows")
@@ -258,8 +326,15 @@ _ap.add_argument("--split", action="store_true",
                  help="with --prefill --gqa: the key-split form and its chunk sweep as well")
 _ap.add_argument("--window", type=int, default=None,
                  help="with --prefill --gqa: the sliding-window form over a prefix of 8192 keys")
+_ap.add_argument("--rope", action="store_true",
+                 help="with --prefill --gqa: rope= beside no RoPE and beside a torch rotation")
 _ap.add_argument("--out", default=None)
 _args = _ap.parse_args()
+if _args.prefill and _args.gqa and _args.rope:
+    prefill_gqa_rope_rows(_args.out or os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gqa_rope",
+        "attn_prefill_gqa_rope.jsonl"))
+    sys.exit(0)
 if _args.prefill and _args.gqa:
     _name = "prefill_gqa_split" if _args.split else "prefill_gqa"
     _dir = "gqa_window" if _args.window else _name

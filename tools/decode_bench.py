@@ -62,6 +62,12 @@ would give; ``us_min`` / ``us_max`` are the spread over the rounds.
 the same keys per workgroup, the time the windowed step should take) and ``copy_window`` (a copy
 of the window's K + V rows). The caches rotate by the window's bytes. ``window_over_short`` stands
 beside ``short_spread``, the min and max round of ``short`` over its median.
+
+``--gqa --rope`` times the rotary step (``rope=``) instead, same rows, to
+``profiles/gqa_rope/attn_decode_gqa_rope.jsonl``: ``fused`` (K rotated in the append launch, Q in
+the split kernel) beside ``plain`` (today's step without RoPE) and ``torch_rope`` (``qkv`` rotated
+in torch with precomputed cos / sin, then ``plain``: what a caller does without ``rope=``).
+``fused_over_plain`` stands beside ``plain_spread``; ``fused_over_torch_rope`` is the saving.
 """
 
 from __future__ import annotations
@@ -638,6 +644,95 @@ def bench_gqa_window_row(B, HQ, KV, D, L, args):
                                            / ref.abs().max())}
 
 
+def rope_table(P, D, device, theta=10000.0):
+    """The plain ``cos | sin`` table ``[P, D]`` fp32 of ``rope=`` (theta-10000 angles)."""
+    import torch
+
+    inv = theta ** (-torch.arange(D // 2, dtype=torch.float64) / (D // 2))
+    ang = torch.arange(P, dtype=torch.float64)[:, None] * inv
+    return torch.cat((ang.cos(), ang.sin()), 1).float().to(device)
+
+
+def rope_qkv_torch(qkv, n_qk, D, rows):
+    """What a caller does without ``rope=``: the first ``n_qk`` (query and key) heads of ``qkv
+    [B, T, heads * D]`` rotated in torch by the table rows ``[T, D]`` (fp32, rotate-half), the
+    value heads carried over: a new ``qkv``."""
+    import torch
+
+    B, T, _ = qkv.shape
+    x = qkv.view(B, T, -1, D)
+    qk, h = x[:, :, :n_qk].float(), D // 2
+    cos = torch.cat((rows[:, :h], rows[:, :h]), 1)[:, None]
+    sin = torch.cat((rows[:, h:], rows[:, h:]), 1)[:, None]
+    rot = torch.cat((-qk[..., h:], qk[..., :h]), -1)
+    return torch.cat(((qk * cos + rot * sin).to(qkv.dtype), x[:, :, n_qk:]), 2).view(B, T, -1)
+
+
+def bench_gqa_rope_row(B, HQ, KV, D, L, args):
+    """``--gqa --rope``: the decode step at context ``L`` with ``rope=`` (``fused``: K rotated in
+    the append launch, Q in the split kernel) beside today's step without RoPE (``plain``) and
+    beside what a caller does today (``torch_rope``: rotate ``qkv`` in torch, then ``plain``), the
+    three alternated in one process as captured graphs of ``--inner`` steps."""
+    import torch
+
+    from distributed_llm_backend_benchmark_amd.ops import decode as dec
+
+    dev = torch.device("cuda", 0)
+    kv_bytes = 2 * B * KV * L * D * 2
+    nbuf = max(1, min(16, -(-args.rotate_mb * (1 << 20) // kv_bytes)))
+    g = torch.Generator(device=dev).manual_seed(L + HQ + KV)
+    caches = [torch.randn(2, B, KV, L, D, generator=g, device=dev).to(torch.bfloat16)
+              for _ in range(nbuf)]
+    qkv = torch.randn(B, 1, (HQ + 2 * KV) * D, generator=g, device=dev).to(torch.bfloat16)
+    length = torch.tensor([L - 1], dtype=torch.int32, device=dev)
+    rope = rope_table(L, D, dev)
+    ws = torch.empty(dec.workspace_numel(B, HQ, D, L, dec.CHUNK_GQA), dtype=torch.float32,
+                     device=dev)
+
+    def step(i, x, **kw):
+        kc, vc = caches[i % nbuf]
+        return dec.decode_attention(x, HQ, kc, vc, length, workspace=ws, n_kv_head=KV, **kw)
+
+    cands = {"plain": lambda i: step(i, qkv), "fused": lambda i: step(i, qkv, rope=rope),
+             "torch_rope": lambda i: step(i, rope_qkv_torch(qkv, HQ + KV, D, rope[L - 1:L]))}
+    graphs = {}
+    for name, fn in cands.items():                       # warm every candidate, then capture
+        for i in range(nbuf + 1):
+            fn(i)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(args.inner):
+                fn(i)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    times = {n: [] for n in graphs}
+    for _ in range(args.rounds):                         # alternate the candidates
+        for name, gr in graphs.items():
+            gr.replay()                                  # untimed: each behind its own traffic
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            gr.replay()
+            e.record()
+            e.synchronize()
+            times[name].append(s.elapsed_time(e) * 1e3 / args.inner)
+    us = {n: statistics.median(v) for n, v in times.items()}
+    ratio = us["fused"] / us["plain"]
+    spread = [min(times["plain"]) / us["plain"], max(times["plain"]) / us["plain"]]
+    # the fused step against the torch rotation feeding today's step: the same rotation but for the
+    # fp32 order (each rounds Q and K to bf16 once)
+    diff = (cands["fused"](0).float() - cands["torch_rope"](0).float()).abs().max()
+    return {"B": B, "H_q": HQ, "H_kv": KV, "G": HQ // KV, "D": D, "L": L, "kv_bytes": kv_bytes,
+            "rotated_caches": nbuf, "chunk_gqa": dec.CHUNK_GQA, "inner": args.inner,
+            "rounds": args.rounds, "us": us, "us_min": {n: min(v) for n, v in times.items()},
+            "us_max": {n: max(v) for n, v in times.items()},
+            "fused_over_plain": ratio, "plain_spread": spread,
+            "within_plain_spread": bool(spread[0] <= ratio <= spread[1]),
+            "fused_over_torch_rope": us["fused"] / us["torch_rope"],
+            "max_abs_diff_fused_vs_torch_rope": float(diff)}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -648,6 +743,9 @@ def main(argv=None) -> int:
     ap.add_argument("--window", type=int, default=None,
                     help="with --gqa: the sliding-window step instead: window, full, short "
                          "(the unwindowed step at context W), copy_window")
+    ap.add_argument("--rope", action="store_true",
+                    help="with --gqa: the rotary step instead: fused (rope=), plain (no RoPE), "
+                         "torch_rope (qkv rotated in torch, then plain)")
     ap.add_argument("--rows", nargs="*", default=None, metavar="B,H,D,L")
     ap.add_argument("--chunks", type=int, nargs="*", default=[128, 256, 512])
     ap.add_argument("--fp8", action="store_true",
@@ -672,7 +770,9 @@ def main(argv=None) -> int:
                          "profiles/ragged_decode/attn_decode_ragged.jsonl)")
     args = ap.parse_args(argv)
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", *(("gqa_window", "attn_decode_gqa_window.jsonl")
+        args.out = os.path.join(REPO, "profiles", *(("gqa_rope", "attn_decode_gqa_rope.jsonl")
+                                                    if args.gqa and args.rope else
+                                                    ("gqa_window", "attn_decode_gqa_window.jsonl")
                                                     if args.gqa and args.window else
                                                     ("gqa_decode", "attn_decode_gqa.jsonl")
                                                     if args.gqa else
@@ -685,6 +785,18 @@ def main(argv=None) -> int:
             else GQA_ROWS if args.gqa else DEFAULT_ROWS)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
+        for shape in rows if args.gqa and args.rope else ():
+            row = bench_gqa_rope_row(*shape, args)
+            f.write(json.dumps(row) + "\n")
+            f.flush()
+            print("B={} H_q={} H_kv={} D={} L={}: ".format(*shape) +
+                  "  ".join(f"{n} {t:.1f} us [{row['us_min'][n]:.1f}, {row['us_max'][n]:.1f}]"
+                            for n, t in row["us"].items()) +
+                  f"  fused/plain {row['fused_over_plain']:.3f} (plain spread "
+                  f"{row['plain_spread'][0]:.3f} .. {row['plain_spread'][1]:.3f})"
+                  f"  fused/torch_rope {row['fused_over_torch_rope']:.3f}", flush=True)
+        if args.gqa and args.rope:
+            return 0
         for shape in rows if args.gqa and args.window else ():
             row = bench_gqa_window_row(*shape, args)
             f.write(json.dumps(row) + "\n")
